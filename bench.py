@@ -18,8 +18,11 @@ Inputs: every pair of a step is a DISTINCT frame (`distinct_pairs == batch_pairs
 level 0 streams from HBM: `--scenes` seeded synthetic scenes, each presented at distinct cyclic (dx, dy)
 shifts - the same shift for the left and the right image, which keeps the pair rectified.
 
-Prints ONE JSON line on rank 0 (see the driver contract).  Extra objects:
-  roofline      dominant kernel (FAST cells): algorithmic bytes per launch / HIP-event duration vs 8 TB/s
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times `--steps` steps and prints the
+line: the headline with the `kernels` / `roofline` figures read from its own timed region.  `--dump-outputs DIR` writes what the
+last timed step delivered (dump_outputs).  Everything that takes runs of its own comes with `--full` (each leg can still be
+left out with its `--no-*` switch):
+  roofline      dominant kernel (FAST cells): algorithmic bytes per launch / HIP-event duration vs 8 TB/s (every run)
   cpu_baseline  the oracle (restated CPU path of the reference) timed on this box's host cores (rank 0, after the last barrier)
   host_in       the same workload with the frames in pinned host memory (H2D inside the timed region)
   workloads     (N = 1) the other workloads BASELINE.json's north_star names, a few steps each after the headline region:
@@ -27,6 +30,7 @@ Prints ONE JSON line on rank 0 (see the driver contract).  Extra objects:
                 lapping area + both SearchByProjection searches per frame, latency mode), dense_1280x720_nf2000 (mosaic
                 frames with ~10 k FAST survivors at level 0, SURVEY a4's range) and planes_1280x720_nf2000 (60 % of the
                 left keypoints find a stereo partner) - each with its own cpu_baseline sample
+  latency       (N = 1) one stereo pair in, results out
 """
 import argparse
 import json
@@ -202,6 +206,45 @@ def make_stream(alloc, w, h, rank, D, scenes, density=1.0, mosaic=0, planes=Fals
             hostL[d] = np.roll(L, (dy, dx), (0, 1))
             hostR[d] = np.roll(R, (dy, dx), (0, 1))
     return hostL, hostR, base
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this much in all (64 MB)
+DUMP_SEED = 0             # the pairs whose results are written, when not all of them fit
+
+
+def dump_outputs(path, fe, B):
+    """--dump-outputs: what the front end `fe` delivered for its last batch of B pairs - the host arrays a caller of
+    ft_stereo_frontend_* receives (StereoFrontend.process) - as DIR/<name>.npy in float32 / float64, so that two builds can be
+    compared output for output:
+      counts             (B, 3) float64  left keypoints, right keypoints, stereo matches of every pair
+      pairs              (k,) float64    the pairs written below, ascending: all of them, or a sample of the seed DUMP_SEED
+                                         as large as DUMP_BYTES holds at the front end's keypoint capacity
+      keys_left/_right   (n, 7) float32  x, y, size, angle, response, octave, class_id of the pairs' keypoints, pair after pair
+      desc_left/_right   (n, 32) float32 descriptor bytes
+      uright, depth      (n_left,) float32  mvuRight / mvDepth
+    Returns the bytes written."""
+    cap = fe.capacity
+    fields = list(fe._kL.dtype.names)
+    per_pair = 4 * cap * (2 * (len(fields) + 32) + 2)   # worst case of one pair at capacity
+    k = int(max(1, min(B, (DUMP_BYTES - 32 * B) // per_pair)))   # (counts and pairs: 32 bytes per pair at most)
+    pick = np.arange(B) if k >= B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, k, replace=False))
+    nL, nR = fe._nL[:B], fe._nR[:B]
+
+    def keys(a, n):
+        return np.concatenate([np.stack([a[b, :n[b]][f].astype(np.float32) for f in fields], -1) for b in pick])
+
+    def rows(a, n):
+        return np.concatenate([a[b, :n[b]].astype(np.float32) for b in pick])
+    arrays = {"counts": np.stack([nL, nR, fe._nm[:B]], -1).astype(np.float64), "pairs": pick.astype(np.float64),
+              "keys_left": keys(fe._kL, nL), "keys_right": keys(fe._kR, nR),
+              "desc_left": rows(fe._dL, nL), "desc_right": rows(fe._dR, nR),
+              "uright": rows(fe._ur, nL), "depth": rows(fe._dp, nL)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def stereo_leg(orb, ctx, name, w, h, nf, B, steps, warmup, mosaic=0, planes=False, scenes=8, cpu_budget_s=4.0, cpu=True):
@@ -778,6 +821,10 @@ def main():
     ap.add_argument("--scene", default="objects", choices=["objects", "planes"],
                     help="objects: every object at a disparity of its own (keypoints on occlusion edges, ~10 %% of the left keypoints "
                          "match); planes: the same scene on fronto-parallel planes (synth.make_planes_pair: ~60 %% match)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that take runs of their own: host_in, the extra workloads, latency, cpu_baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step delivered to DIR/<name>.npy (rank 0's shard; see dump_outputs)")
     ap.add_argument("--no-workloads", action="store_true", help="skip the extra workloads (752x480, tracking 512x512, dense, planes)")
     ap.add_argument("--workload-batch", type=int, default=512, help="pairs per step of the extra stereo workloads")
     ap.add_argument("--workload-frames", type=int, default=48, help="frames per threshold of the tracking workload")
@@ -892,6 +939,8 @@ def main():
     elapsed_rank = timed(args.steps, ptrsL, ptrsR, True)
     steady_rank = steady_rate()
     ctx.set_kernel_timing(False)
+    if args.dump_outputs and rank == 0:   # every step runs the same batch: the front end of the last step holds its results
+        dump_outputs(args.dump_outputs, fes[(args.steps - 1) % len(fes)], B)
     kps_rank = int(fe._nL[:B].sum() + fe._nR[:B].sum())  # keypoints of one pass over this rank's batch
     matches = int(fe._nm[:B].sum())
 
@@ -919,7 +968,7 @@ def main():
     # do (cv::Mat, src/Frame.cc:442-449; the reference uploads per call, src/ORBextractor.cc:1522-1541): the H2D copies
     # of all 2 B frames of a step are inside the timed region.  Never the headline value.
     host_in = None
-    if not args.no_host_in:
+    if args.full and not args.no_host_in:
         hsteps = max(2, min(args.steps, 12))
         run(2, hptrsL, hptrsR, False)
         ctx.reset_stats()
@@ -1050,7 +1099,7 @@ def main():
         # headline's buffers are released first; every leg builds and releases its own.
         out["workloads"] = None
         out["latency"] = None
-        if world == 1 and not args.no_workloads:
+        if args.full and world == 1 and not args.no_workloads:
             for f in fes:
                 f.close()
             devL.free()
@@ -1069,7 +1118,7 @@ def main():
             wl["planes_1280x720_nf2000"] = stereo_leg(orb, ctx, "planes", 1280, 720, 2000, WB, 16, 4, planes=True, cpu=cpu, cpu_budget_s=3.0)
             out["workloads"] = wl
             out["latency"] = latency_leg(orb, ctx)
-        if not args.no_cpu_baseline:  # rank 0, after the last barrier: the other ranks are done and the host cores are free
+        if args.full and not args.no_cpu_baseline:  # rank 0, after the last barrier: the other ranks are done and the host cores are free
             out["cpu_baseline"] = cpu_baseline(w, h, nf, pairs)
             out["gpu_over_cpu_per_gpu"] = fps / world / out["cpu_baseline"]["value"]
             if world == 1:

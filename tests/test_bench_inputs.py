@@ -47,3 +47,39 @@ def test_mosaic_pair_is_dense_seeded_and_rectified():
     exd.extract(L)
     exo.extract(obj)
     assert len(exd.candidates(0)) > 3 * len(exo.candidates(0))  # several times the FAST survivors of the object scenes
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs on a batch too large to write whole: a fixed seeded sample of the pairs, at most 64 MB even with every
+    image at the front end's keypoint capacity, the arrays of each sampled pair as the front end holds them"""
+    from types import SimpleNamespace
+    from fasttrack_amd import KP_DTYPE
+    bench = _bench()
+    B, cap = 300, 2100
+    rng = np.random.default_rng(3)
+    kL, kR = np.zeros((B, cap), KP_DTYPE), np.zeros((B, cap), KP_DTYPE)
+    for k in (kL, kR):
+        for f in ("x", "y", "size", "angle", "response"):
+            k[f] = rng.random((B, cap), np.float32)
+        k["octave"] = rng.integers(0, 8, (B, cap))
+        k["class_id"] = -1
+    fe = SimpleNamespace(capacity=cap, _kL=kL, _kR=kR, _dL=rng.integers(0, 256, (B, cap, 32), np.uint8),
+                         _dR=rng.integers(0, 256, (B, cap, 32), np.uint8), _ur=rng.random((B, cap), np.float32),
+                         _dp=rng.random((B, cap), np.float32), _nL=np.full(B, cap, np.int32), _nR=np.full(B, cap, np.int32),
+                         _nm=rng.integers(0, cap, B).astype(np.int32))
+    total = bench.dump_outputs(str(tmp_path / "a"), fe, B)
+    bench.dump_outputs(str(tmp_path / "b"), fe, B)
+    names = sorted(os.listdir(tmp_path / "a"))
+    d = {n[:-4]: np.load(os.path.join(tmp_path, "a", n)) for n in names}
+    assert total == sum(v.nbytes for v in d.values()) <= 64e6 and total > 48e6
+    assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+    for n in names:
+        assert np.array_equal(np.load(os.path.join(tmp_path, "a", n)), np.load(os.path.join(tmp_path, "b", n))), n
+    pick = d["pairs"].astype(int)
+    assert 1 < len(pick) < B and np.all(np.diff(pick) > 0) and pick[-1] < B
+    assert np.array_equal(d["counts"], np.stack([fe._nL, fe._nR, fe._nm], -1))
+    j = 1  # the second sampled pair
+    b, rows = pick[j], slice(j * cap, (j + 1) * cap)
+    assert np.array_equal(d["keys_left"][rows, 5], kL[b]["octave"]) and np.array_equal(d["keys_right"][rows, 0], kR[b]["x"])
+    assert np.array_equal(d["desc_right"][rows], fe._dR[b]) and np.array_equal(d["uright"][rows], fe._ur[b])
+    assert np.array_equal(d["depth"][rows], fe._dp[b]) and d["keys_left"].shape == (len(pick) * cap, 7)

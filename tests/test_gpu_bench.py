@@ -1,5 +1,6 @@
 """bench.py on the GPU box: the N>1 launch path through the real library (two ranks folded onto the one device
-of the box with FT_BENCH_DEVICE_MOD=1), the contract fields of the JSON line, and the host-in leg."""
+of the box with FT_BENCH_DEVICE_MOD=1), the contract fields of the JSON line, the host-in leg (--full), and a plain run with
+the outputs of its last step (--dump-outputs)."""
 import json
 import os
 import subprocess
@@ -22,7 +23,7 @@ def _run(args, env_extra=None, timeout=900):
 
 
 def test_bench_two_ranks_folded_onto_one_device():
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16", "--workload", "stereo_640x480_nf1000",
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16", "--workload", "stereo_640x480_nf1000", "--full",
               "--no-cpu-baseline"], {"FT_BENCH_DEVICE_MOD": "1"})
     assert r["workloads"] is None  # N = 1 only
     assert r["n_gpus"] == 2 and r["scaling"] == "weak" and r["steps"] == 3
@@ -38,8 +39,10 @@ def test_bench_eight_ranks_folded_onto_one_device():
     """the shape of the driver's 8-GPU run on the one device of the box: eight processes, eight contexts with their lane
     tables and thread pools (cpus / 8 each), gloo rendezvous, NUMA pinning of every rank, the cpu_baseline leg on rank 0
     after the last barrier - so that the first real 8-GPU run does not die on ports, pinned-memory limits or queue counts"""
-    r = _run(["--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "24", "--workload", "stereo_752x480_nf1200", "--no-host-in"],
-             {"FT_BENCH_DEVICE_MOD": "1"}, timeout=1500)
+    # GPU_MAX_HW_QUEUES: the value the Python driver exports when the variable is unset; set here because the test's own
+    # environment may carry another one, which the driver leaves alone
+    r = _run(["--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "24", "--workload", "stereo_752x480_nf1200", "--full", "--no-host-in"],
+             {"FT_BENCH_DEVICE_MOD": "1", "GPU_MAX_HW_QUEUES": "10"}, timeout=1500)
     assert r["n_gpus"] == 8 and r["scaling"] == "weak" and len(r["per_rank_frames_per_s"]) == 8 and min(r["per_rank_frames_per_s"]) > 0
     assert r["value"] <= sum(r["per_rank_frames_per_s"]) * 1.0001 and r["device_octree_fallbacks"] == 0
     assert r["workloads"] is None and r["cpu_baseline"]["value"] > 0 and r["cpu_baseline"]["kind"] == "port"
@@ -56,8 +59,52 @@ def test_bench_four_ranks_folded_onto_one_device():
     assert "numa_node_of_rank0" in r["config"] and "no collective" in r["config"]["parallelism"]
 
 
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """a run without --full: the headline alone over exactly `--steps` timed steps; --dump-outputs writes what the last of them
+    delivered - the same arrays in two runs with the same arguments, and the oracle's results for the frames of the batch"""
+    import importlib.util
+    import numpy as np
+    from oracle import binding as ob
+    B, steps = 12, 4
+    args = ["--steps", str(steps), "--warmup", "1", "--batch", str(B), "--workload", "stereo_640x480_nf1000"]
+    runs = [(_run(args + ["--dump-outputs", str(tmp_path / d)]), tmp_path / d) for d in ("a", "b")]
+    names = {"counts", "pairs", "keys_left", "keys_right", "desc_left", "desc_right", "uright", "depth"}
+    dumps = []
+    for r, d in runs:
+        assert r["steps"] == steps and r["n_gpus"] == 1 and r["metric"] == "frames/sec extract+match" and r["higher_is_better"] is True
+        assert abs(r["ms_per_step"] * r["value"] - 1e3 * B) < 1e-6 * 1e3 * B   # ms_per_step = elapsed / steps, value = B * steps / elapsed
+        assert r["host_in"] is None and r["workloads"] is None and r["latency"] is None and r["cpu_baseline"] is None
+        assert {f[:-4] for f in os.listdir(d)} == names
+        a = {n: np.load(os.path.join(d, n + ".npy")) for n in names}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64e6
+        dumps.append(a)
+    a, b = dumps
+    for n in names:
+        assert np.array_equal(a[n], b[n]), n
+    assert np.array_equal(a["pairs"], np.arange(B)) and a["counts"].shape == (B, 3)
+    assert len(a["keys_left"]) == len(a["desc_left"]) == len(a["uright"]) == a["counts"][:, 0].sum() and len(a["keys_right"]) == a["counts"][:, 1].sum()
+    # pair 0 of the batch against the oracle
+    spec = importlib.util.spec_from_file_location("bench_mod_plain", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    w, h, nf, _ = bench.WORKLOADS["stereo_640x480_nf1000"]
+    hostL, hostR, _ = bench.make_stream(lambda shape, dt: np.zeros(shape, dt), w, h, 0, B, 16)
+    intr = bench.synth.intrinsics(w, h)
+    exL, exR = (ob.Extractor(nf, bench.SCALE, bench.NLEVELS, bench.INI_TH, bench.MIN_TH) for _ in range(2))
+    kL, dL, _ = exL.extract(hostL[0])
+    kR, dR, _ = exR.extract(hostR[0])
+    sm = ob.stereo_match(exL, exR, kL, kR, dL, dR, intr["mbf"], intr["mb"])
+    nL, nR = int(a["counts"][0, 0]), int(a["counts"][0, 1])
+    assert (nL, nR, int(a["counts"][0, 2])) == (len(kL), len(kR), sm["n"])
+    for i, f in enumerate(("x", "y", "size", "angle", "response", "octave")):
+        assert np.array_equal(a["keys_left"][:nL, i], kL[f].astype(np.float32)), f
+        assert np.array_equal(a["keys_right"][:nR, i], kR[f].astype(np.float32)), f
+    assert np.array_equal(a["desc_left"][:nL], dL.astype(np.float32)) and np.array_equal(a["desc_right"][:nR], dR.astype(np.float32))
+    assert np.array_equal(a["uright"][:nL], sm["uright"]) and np.array_equal(a["depth"][:nL], sm["depth"])
+
+
 def test_bench_single_rank_line_has_the_contract_fields():
-    r = _run(["--steps", "3", "--warmup", "1", "--batch", "32", "--workload", "stereo_752x480_nf1200", "--no-cpu-baseline",
+    r = _run(["--steps", "3", "--warmup", "1", "--batch", "32", "--workload", "stereo_752x480_nf1200", "--full", "--no-cpu-baseline",
               "--workload-batch", "20", "--workload-frames", "6", "--tracking-batch", "24"])
     assert r["n_gpus"] == 1 and r["metric"] == "frames/sec extract+match" and r["unit"] == "frames/s"
     assert r["dtype"] == "u8" and r["vs_baseline"] is None and r["higher_is_better"] is True

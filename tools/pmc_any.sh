@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc $CNT -d $OUT/sq -o pmc -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --pmc $CNT -d $OUT/sq -o pmc -- python3 $REPO/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline "$@" > $OUT/bench.log 2>&1
 python3 - <<PY
 import sqlite3, glob
 for f in glob.glob("$OUT/sq/**/*.db", recursive=True):
