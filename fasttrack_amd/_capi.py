@@ -202,6 +202,8 @@ def lib() -> C.CDLL:
     L.ft_tracked_frame_track_local_map.argtypes = [vp, C.POINTER(FramePose), C.POINTER(MapPoints), f, f, f, f, i, f,
                                                    C.POINTER(FrustumResult), ip, vp, ip]
     L.ft_tracked_frame_holder_obs.argtypes = [vp, vp]
+    L.ft_search_for_initialization.argtypes = [vp, C.POINTER(FrameView), C.POINTER(FrameView), vp, i, f, i, vp, ip, vp]
+    L.ft_tracked_frame_search_for_initialization.argtypes = [vp, vp, vp, i, f, i, vp, ip]
     L.ft_tracked_batch_create.argtypes = [vp, i, i, i, C.POINTER(vp)]
     L.ft_tracked_batch_destroy.argtypes = [vp]
     L.ft_tracked_batch_upload.argtypes = [vp, i, C.POINTER(FrameView)]

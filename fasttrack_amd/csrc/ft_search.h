@@ -238,7 +238,62 @@ int ft_launch_search_last(hipStream_t st, const FtDevFrame &F, const FtDevLastPo
 int ft_launch_build_grid(hipStream_t st, const FtDevFrame &F, int *gridStartL, int *gridStartR, float4 *recL, uint8_t *descL,
                          float4 *recR, uint8_t *descR);
 
+// ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:747-862; kernels_init.hip).  A ROW is a level-0 keypoint of F1, in index
+// order; an ORD is the rank of a level-0 keypoint of F2's grid in the order (cell column, cell row, index) - the order
+// Frame::GetFeaturesInArea returns the keypoints of ANY window in, so "the first of equal distances" is "the smallest ord".
+// A candidate is one word: distance << FT_INIT_ORD_BITS | ord.  cap1 / cap2 bound rows / ords (the host's counts of the
+// level-0 keypoints): every table below has that many entries and no kernel writes beyond them.
+#define FT_INIT_ORD_BITS 22
+#define FT_INIT_NONE 0xffffffffu
+#define FT_INIT_TOP 4  // candidates of a row the resolution looks at before it reads the row's segment
+struct FtInitSearch {
+    FtDevFrame F2;  // the current frame with its grid
+    const ft_keypoint *keys1;
+    const uint8_t *desc1;
+    int N1;
+    const float *prev;  // [N1][2] vbPrevMatched on entry
+    float window, nnRatio;
+    int checkOrientation;
+    int cap1, cap2;
+    int *counts;        // [0] rows, [1] ords (both clamped to the caps), [2] != 0: the device counted more than the caps admit
+    int *rows;          // [cap1] keypoint of F1 of a row
+    int *ordOfPos;      // [cap2] ord of the entry at position p of octave 0 of F2's grid
+    int *idxOfOrd;      // [cap2] keypoint of F2 of an ord
+    unsigned *seg;      // [cap1][cap2] the candidates of a row, unordered
+    int *segCount;      // [cap1]
+    unsigned *top;      // [cap1][FT_INIT_TOP] the smallest candidates of a row, ascending (FT_INIT_NONE = none)
+    int *matches12;     // [N1]
+    float *prevOut;     // [N1][2]
+    int *matchedDist;   // [F2.N] vMatchedDistance (INT_MAX = unmatched)
+    int *nMatches;      // [1]
+};
+// the three launches of a call, in this order; ldsBytes = 4 * (cap1 + cap2)
+int ft_launch_init_prepare(hipStream_t st, const FtInitSearch &S);
+int ft_launch_init_candidates(hipStream_t st, const FtInitSearch &S);
+int ft_launch_init_resolve(hipStream_t st, const FtInitSearch &S);
+#define FT_INIT_MAX_LDS (150 * 1024)
+
 #ifdef __HIPCC__
+struct Window {
+    int minCX, maxCX, minCY, maxCY;
+    bool empty;
+};
+
+// Frame::GetFeaturesInArea cell window (src/Frame.cc:689-711)
+__device__ __forceinline__ Window cell_window(const FtDevFrame &F, float x, float y, float r) {
+    Window w;
+    w.empty = false;
+    w.minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, F.mnMinX), r), F.invW)));
+    if (w.minCX >= FT_GRID_COLS) w.empty = true;
+    w.maxCX = min(FT_GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, F.mnMinX), r), F.invW)));
+    if (w.maxCX < 0) w.empty = true;
+    w.minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, F.mnMinY), r), F.invH)));
+    if (w.minCY >= FT_GRID_ROWS) w.empty = true;
+    w.maxCY = min(FT_GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F.mnMinY), r), F.invH)));
+    if (w.maxCY < 0) w.empty = true;
+    return w;
+}
+
 // Re-derives a pointer read from a job record from the arena pointer the kernel got as an argument (kernels_search.hip: a
 // pointer out of memory is a generic pointer to the compiler): arena + (p - address of the arena, passed as an integer)
 struct Rebase {

@@ -169,26 +169,6 @@ __device__ __forceinline__ void claims_file(const FtClaims &C, int *res, int i, 
 
 __device__ __forceinline__ unsigned div_magic_u(int d) { return d > 1 ? 0xffffffffu / (unsigned)d + 1u : 0u; }
 
-struct Window {
-    int minCX, maxCX, minCY, maxCY;
-    bool empty;
-};
-
-// Frame::GetFeaturesInArea cell window (src/Frame.cc:689-711)
-__device__ __forceinline__ Window cell_window(const FtDevFrame &F, float x, float y, float r) {
-    Window w;
-    w.empty = false;
-    w.minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, F.mnMinX), r), F.invW)));
-    if (w.minCX >= FT_GRID_COLS) w.empty = true;
-    w.maxCX = min(FT_GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, F.mnMinX), r), F.invW)));
-    if (w.maxCX < 0) w.empty = true;
-    w.minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, F.mnMinY), r), F.invH)));
-    if (w.minCY >= FT_GRID_ROWS) w.empty = true;
-    w.maxCY = min(FT_GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F.mnMinY), r), F.invH)));
-    if (w.maxCY < 0) w.empty = true;
-    return w;
-}
-
 // geometric part of GetFeaturesInArea for one keypoint: grid cell (Frame::PosInGrid, :749-759) inside
 // the window, level band, box test.  Returns false when the keypoint is not a candidate.
 __device__ __forceinline__ bool in_area(const FtDevFrame &F, const ft_keypoint &kp, const Window &w, float x, float y,

@@ -444,6 +444,20 @@ class KernelController:
         return r
 
     @staticmethod
+    def search_for_initialization(ctx: Context, F1: FrameView, F2: FrameView, prev_matched, window=100, nn_ratio=0.9,
+                                  check_orientation=True):
+        """ORBmatcher(nn_ratio, check_orientation).SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, window)
+        (ORBmatcher.cc:747-862) -> dict(matches12, prev_matched (the updated copy), n, matched_distance)."""
+        N1, N2 = F1.c.N, F2.c.N
+        prev = np.array(prev_matched, np.float32).reshape(N1, 2).copy()
+        m12 = np.full(max(N1, 1), -1, np.int32)
+        dist = np.zeros(max(N2, 1), np.int32)
+        n = C.c_int()
+        check(lib().ft_search_for_initialization(ctx._h, C.byref(F1.c), C.byref(F2.c), ptr(prev) if N1 else None, int(window),
+                                                 float(nn_ratio), int(check_orientation), ptr(m12), C.byref(n), ptr(dist)))
+        return dict(matches12=m12[:N1], prev_matched=prev, n=n.value, matched_distance=dist[:N2])
+
+    @staticmethod
     def descriptor_distance(ctx: Context, a, b):
         a, b = np.ascontiguousarray(a, np.uint8), np.ascontiguousarray(b, np.uint8)
         n = len(a)
@@ -688,6 +702,17 @@ class TrackedFrame:
             check(lib().ft_tracked_frame_search_last_frame(self._h, C.byref(Lp), ptr(T), th, int(forward), int(backward),
                                                            int(check_orientation), ptr(assign), C.byref(n)))
         return dict(assign=assign[:self.N], n=n.value)
+
+    def search_for_initialization(self, initial: "TrackedFrame", prev_matched, window=100, nn_ratio=0.9, check_orientation=True):
+        """SearchForInitialization(initial, self, ...) on two resident frames (ft_tracked_frame_search_for_initialization)
+        -> dict(matches12, prev_matched (the updated copy), n)."""
+        N1 = initial.N
+        prev = np.array(prev_matched, np.float32).reshape(N1, 2).copy()
+        m12 = np.full(max(N1, 1), -1, np.int32)
+        n = C.c_int()
+        check(lib().ft_tracked_frame_search_for_initialization(self._h, initial._h, ptr(prev) if N1 else None, int(window),
+                                                               float(nn_ratio), int(check_orientation), ptr(m12), C.byref(n)))
+        return dict(matches12=m12[:N1], prev_matched=prev, n=n.value)
 
     def track_local_map(self, pose, pts: dict, viewing_cos_limit, log_scale_factor, th, nn_ratio=0.8, far_points=False,
                         th_far_points=0.0):

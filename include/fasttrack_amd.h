@@ -394,6 +394,26 @@ FT_API int ft_search_last_frame_se3(ft_context *ctx, ft_frame_view *Cur, const f
                                     int *n_matches, int *best_dist, int *best_idx, int *best_dist_r, int *best_idx_r);
 
 /* ------------------------------------------------------------------------------------------------
+ * ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (src/ORBmatcher.cc:747-862), the
+ * matcher Tracking::MonocularInitialization calls on every frame until the map exists (src/Tracking.cc:2516-2549:
+ * ORBmatcher matcher(0.9, true); windowSize 100).  For the level-0 keypoints of F1 IN INDEX ORDER: the candidates
+ * F2.GetFeaturesInArea(prev.x, prev.y, windowSize, 0, 0) in that function's order, a candidate held at a distance that is not
+ * larger is skipped (:786), best / second best with strict <, TH_LOW = 50 and bestDist < (float)bestDist2 * nn_ratio (:801-803);
+ * a strictly closer keypoint takes the match away from its owner, who stays unmatched (:805-813) but stays in its rotation bin
+ * (:817-825); ComputeThreeMaxima and the removal (:831-854), then vbPrevMatched[i1] = F2.mvKeysUn[vnMatches12[i1]].pt (:857-859).
+ * Of F1 only N, keys (octave, angle) and descriptors are read; F2 is a mono / rectified view (Nleft == -1): N, keys,
+ * descriptors, the image bounds and grid constants, nlevels.  prev_matched: N1 x 2 floats, in/out; matches12: N1 ints
+ * (vnMatches12); *n_matches: the return value; matched_distance (may be NULL): F2->N ints, vMatchedDistance as the loop leaves
+ * it (INT_MAX where unmatched).  Everything equals the reference bit for bit.
+ * Launches per call: 4 (the grid of F2, then three kernels: rows and candidate order, the candidates of every row, the
+ * sequential resolution with histogram and outputs) - a fixed sequence, one wait; kernel timing names them kernel.init_*.
+ * FT_ERR_CAPACITY when the two frames together hold more than 38400 level-0 keypoints (65534 in F1).
+ * ---------------------------------------------------------------------------------------------- */
+FT_API int ft_search_for_initialization(ft_context *ctx, const ft_frame_view *F1, const ft_frame_view *F2, float *prev_matched,
+                                        int window_size, float nn_ratio, int check_orientation, int *matches12, int *n_matches,
+                                        int *matched_distance);
+
+/* ------------------------------------------------------------------------------------------------
  * Frustum test + scale prediction for the local map points: Frame::isInFrustum /
  * isInFrustumChecks (src/Frame.cc:536-610, 1308-1382) with MapPoint::PredictScale (src/MapPoint.cc:531-546),
  * the host loop in front of SearchByProjection (src/Tracking.cc:3503-3522).
@@ -469,6 +489,14 @@ FT_API int ft_tracked_frame_track_local_map(ft_tracked_frame *tf, const ft_frame
                                             float viewing_cos_limit, float log_scale_factor, float th, float nn_ratio,
                                             int far_points, float th_far_points, const ft_frustum_result *frustum,
                                             int *n_to_match, int *assign, int *n_matches);
+/* ft_search_for_initialization on two resident frames: `initial` (mInitialFrame, uploaded once when it is set) and `current`
+ * (uploaded per frame), both by ft_tracked_frame_upload with Nleft == -1 on one context.  Nothing of either frame is marshalled
+ * again: prev_matched goes up; matches12, prev_matched and *n_matches come back.  holder_obs of both frames is neither read nor
+ * written.  Launches per call: 3 (4 for a current frame loaded under option search_grid = 0: its grid is built for the call);
+ * statistic "tracked.search_for_initialization.launches" sums them.  A frame without level-0 keypoints returns without a launch. */
+FT_API int ft_tracked_frame_search_for_initialization(ft_tracked_frame *current, ft_tracked_frame *initial, float *prev_matched,
+                                                      int window_size, float nn_ratio, int check_orientation, int *matches12,
+                                                      int *n_matches);
 /* current holder_obs (size N of the resident frame) */
 FT_API int ft_tracked_frame_holder_obs(ft_tracked_frame *tf, int *holder_obs);
 

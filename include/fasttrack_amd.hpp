@@ -337,6 +337,21 @@ public:
         assign.resize(N_);
         return nm;
     }
+    // ORBmatcher(mfNNratio, mbCheckOrientation).SearchForInitialization(F1, *this, vbPrevMatched, vnMatches12, windowSize)
+    // with *this as the current frame F2 and F1 = mInitialFrame, both resident           ORBmatcher.cc:747, Tracking.cc:2516-2549
+    // Point2f: cv::Point2f or anything else made of two floats x, y.
+    template <class Point2f>
+    int SearchForInitialization(TrackedFrame &F1, std::vector<Point2f> &vbPrevMatched, std::vector<int> &vnMatches12, int windowSize,
+                                float mfNNratio = 0.9f, bool mbCheckOrientation = true) {
+        static_assert(sizeof(Point2f) == 2 * sizeof(float), "vbPrevMatched must hold two floats per keypoint");
+        if ((int)vbPrevMatched.size() != F1.N_) throw Error(FT_ERR_INVALID, "vbPrevMatched must hold one point per keypoint of F1");
+        vnMatches12.assign(F1.N_ > 0 ? F1.N_ : 1, -1);
+        int nm = 0;
+        check(ft_tracked_frame_search_for_initialization(h_, F1.h_, reinterpret_cast<float *>(vbPrevMatched.data()), windowSize,
+                                                         mfNNratio, mbCheckOrientation ? 1 : 0, vnMatches12.data(), &nm));
+        vnMatches12.resize(F1.N_);
+        return nm;
+    }
     std::vector<int> holderObservations() {
         std::vector<int> h(N_ > 0 ? N_ : 1);
         check(ft_tracked_frame_holder_obs(h_, h.data()));
