@@ -1,4 +1,4 @@
-// Device-side views used by the projection-search kernels (kernels_search.hip / search.cpp).
+// Device-side views used by the projection-search kernels (kernels_search.hip / search_host.h).
 #pragma once
 
 #include "ft_internal.h"
@@ -117,7 +117,7 @@ struct FtFrustumOut {
     int *count;           // nToMatch (atomic; zeroed by the launcher)
 };
 
-// One frame of a batch of searches (ft_tracked_batch, search.cpp): what the batch kernels read of frame blockIdx.y, resident
+// One frame of a batch of searches (ft_tracked_batch, tracked_batch.cpp): what the batch kernels read of frame blockIdx.y, resident
 // in HBM.  Every pointer of a job points into the device arena of its batch (`arena` of the launchers below: the kernels
 // re-derive the pointers from it, see Rebase in kernels_search.hip).  The rotating buffers of the claim iteration are addressed by pass number (job_claims, kernels_search.hip):
 // res 2 x 4 nPoints | head 3 x K | next 2 x 4 nPoints | tab 3 x 8 K (K = keypoints rounded up to 8) | flags FT_BATCH_FLAGS.

@@ -34,7 +34,7 @@ __device__ __forceinline__ int hamming256(const unsigned long long a[4], const u
 // a cast through the global address space nor llvm.assume(!is_shared && !is_private) survives the optimiser.  What does:
 // re-deriving the pointer from a pointer that IS a kernel argument - the batch's device arena, with the arena's address
 // passed a second time as a plain integer, so that arena + (p - address) cannot be folded back into p.  Everything a job
-// record points to lies inside the arena of its batch (search.cpp).
+// record points to lies inside the arena of its batch (tracked_batch.cpp).
 struct NoRebase {  // the pointers are kernel arguments already
     template <class T>
     __device__ __forceinline__ T *operator()(T *p) const {
@@ -65,7 +65,7 @@ __device__ __forceinline__ FramePtrs frame_ptrs(const FtDevFrame &F, const RB &r
 #define KEY_NONE 0xffffffffffffffffull
 // Candidate key: (distance, cell x, cell y, index) in the high bits - ascending keys are the scan order of the CPU loop, see
 // the header - and below them what a later pass would otherwise have to fetch again through dependent loads: the keypoint's
-// octave (four bits: checkFrame, search.cpp, admits octaves of [0, nlevels) only; masked here so that the keypoints of a
+// octave (four bits: checkFrame, search_host.h, admits octaves of [0, nlevels) only; masked here so that the keypoints of a
 // BOUND frame, which no host check sees, can never spill into the index) and whether it was held before the call
 // (mvpMapPoints[idx]->Observations() > 0).  The index is unique inside a window, so the low bits never decide a comparison.
 __device__ __forceinline__ unsigned long long make_key(int dist, int cx, int cy, int idx, int octave, bool heldBefore) {
@@ -1027,7 +1027,7 @@ __global__ __launch_bounds__(256) void k_last_project_batch(const FtBatchJob *__
 // One frame at a time leaves the chip idle by construction: a pass of the claim iteration is ~500 workgroups and a handful
 // of dependent L2 round trips, 9 - 13 passes per search, each a launch.  Here blockIdx.y is the FRAME: everything a pass
 // needs of a frame - the frame itself, its points, its rotating claim buffers - sits in a job record in HBM (read through
-// scalar loads: the address is uniform), the pass number selects the buffers exactly as fixedPoint (search.cpp) does for a
+// scalar loads: the address is uniform), the pass number selects the buffers exactly as fixedPoint (search_host.h) does for a
 // launch of its own, and every frame has its own convergence flags, so that the workgroups of a frame whose iteration has
 // reached its fixed point return at once while the other frames go on: the batch runs max-over-frames passes.
 __device__ __forceinline__ FtClaims job_claims(const FtBatchJob &J, const Rebase &rb, int pass, int fCur, int fPrev, int fReset, int *&res) {
@@ -2083,7 +2083,7 @@ __global__ __launch_bounds__(FT_RS_LANES) void k_resolve_batch(const FtBatchJob 
 }
 
 // ---- the writes of a converged search, replayed where the results are ------------------------------------------------------------
-// What the host did with a search's results until round 5 (replayLocalWrites / replayLastFrameWrites, search.cpp) - and what
+// What the host did with a search's results until round 5 (replayLocalWrites / replayLastFrameWrites, search_host.h) - and what
 // the reference does while it searches: CurrentFrame.mvpMapPoints[kp] = pMP in point order (src/ORBmatcher.cc:134-148, 203-214;
 // 1860-1879, 1934-1941), the rotation histogram (:1880-1896, 1942-1957), ComputeThreeMaxima (:2210-2251) and the removal of
 // the matches outside the three dominant bins (:1966-1987).  A workgroup per frame:
@@ -2347,7 +2347,7 @@ __global__ __launch_bounds__(256) void k_fill_i32(int *p, int n, int v) {
 }
 
 // start of the claim iteration of every frame of a batch (blockIdx.y = frame): list heads and writer table = -1 (27 K words
-// behind J.head: layoutBatch, search.cpp), the frame's FT_BATCH_FLAGS flag words = -1, the cache's meta words = ~0, the frustum count = 0
+// behind J.head: layoutBatch, tracked_batch.cpp), the frame's FT_BATCH_FLAGS flag words = -1, the cache's meta words = ~0, the frustum count = 0
 __global__ __launch_bounds__(256) void k_fill_claims_batch(const FtBatchJob *__restrict__ jobs, Rebase rb) {
     const FtBatchJob &J = jobs[blockIdx.y];
     const int t = blockIdx.x * 256 + threadIdx.x, T = gridDim.x * 256;
@@ -2645,7 +2645,7 @@ int ft_launch_search_last(hipStream_t st, const FtDevFrame &F, const FtDevLastPo
     return FT_OK;
 }
 
-// ---- launches of a batch of frames (ft_tracked_batch, search.cpp) ----
+// ---- launches of a batch of frames (ft_tracked_batch, tracked_batch.cpp) ----
 int ft_launch_fill_claims_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxWords);
 #define FT_SLOW_BLOCKS 16  // workgroups per frame of a slow-list launch (a grid-stride loop serves longer lists)
 static Rebase rebase_of(void *arena) { return Rebase{(uint8_t *)arena, (unsigned long long)(uintptr_t)arena}; }
