@@ -1,4 +1,5 @@
-// Device-side views used by the projection-search kernels (kernels_search.hip / search_host.h).
+// Device-side views used by the projection-search kernels (kernels_search.hip, kernels_search_rows.hip, kernels_resolve.hip,
+// kernels_frame.hip) and their host side (search_host.h), and the launches of those kernels.
 #pragma once
 
 #include "ft_internal.h"
@@ -59,7 +60,7 @@ struct FtClaims {
     int firstPass;           // no lists yet: the pre-call holders decide, and every result counts as changed
     int *headWrite, *nextWrite;  // lists this pass builds for the next one
     int *headClear;          // the heads the next pass will write: reset to -1 here
-    // the writer table (kernels_search.hip, FT_TAB_ENTRIES): 8 ints per keypoint, rotating like the heads; head / next
+    // the writer table (search_dev.h, FT_TAB_ENTRIES): 8 ints per keypoint, rotating like the heads; head / next
     // only take the writers a record has no room for
     const int *tab;
     int *tabWrite, *tabClear;
@@ -68,7 +69,7 @@ struct FtClaims {
     int *flagCur;            // this pass's flag (atomicAnd 0 on a change)
     const int *flagPrev;     // the previous pass's flag (null for the first pass of a burst)
     int *flagReset;          // the flag of the same position in the other burst parity: reset to -1 here
-    int *flagStick = nullptr;  // batch form only: the 16 flag words of this burst (claims_begin_pass, kernels_search.hip)
+    int *flagStick = nullptr;  // batch form only: the 16 flag words of this burst (claims_begin_pass, search_dev.h)
     // Candidate cache (may be null).  What does NOT change from pass to pass - which keypoints of a point's window pass the
     // level band, the box and the uright test, and their Hamming distances - is computed once: the first pass that reaches a
     // (point, camera) window files the (distance, cell x, cell y, index) keys of all its candidates here, and every later
@@ -100,7 +101,7 @@ struct FtLastRaw {
     int *bestDist, *bestIdx, *bestDistR, *bestIdxR;
 };
 
-// Frame::isInFrustum inputs / outputs (kernels_search.hip k_frustum)
+// Frame::isInFrustum inputs / outputs (kernels_frame.hip k_frustum)
 struct FtDevMapPoints {
     int M;
     const uint8_t *skip;  // may be null
@@ -119,7 +120,7 @@ struct FtFrustumOut {
 
 // One frame of a batch of searches (ft_tracked_batch, tracked_batch.cpp): what the batch kernels read of frame blockIdx.y, resident
 // in HBM.  Every pointer of a job points into the device arena of its batch (`arena` of the launchers below: the kernels
-// re-derive the pointers from it, see Rebase in kernels_search.hip).  The rotating buffers of the claim iteration are addressed by pass number (job_claims, kernels_search.hip):
+// re-derive the pointers from it, see FramePtrs in search_dev.h).  The rotating buffers of the claim iteration are addressed by pass number (job_claims, search_dev.h):
 // res 2 x 4 nPoints | head 3 x K | next 2 x 4 nPoints | tab 3 x 8 K (K = keypoints rounded up to 8) | flags FT_BATCH_FLAGS.
 // projection of a last-frame point into the current frame's camera(s) (k_last_project_batch, kernels_search.hip)
 struct FtLastProj {
@@ -186,7 +187,7 @@ int ft_launch_bind_fisheye_batch(hipStream_t st, void *arena, const FtBatchJob *
 // where the depth is > 0.0001, fills mvRightToLeftMatch, mvDepth, mvStereo3Dpoints and the frame's match count
 int ft_launch_fisheye_triangulate_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxKp, const FtBindArgs &A);
 int ft_launch_fill_claims_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxWords);
-// behind the first pass of a batch: every candidate list with its best candidates at the front (cache_partition, kernels_search.hip)
+// behind the first pass of a batch: every candidate list with its best candidates at the front (cache_partition, kernels_search_rows.hip)
 int ft_launch_cache_partition_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxPoints);
 int ft_launch_deliver_batch(hipStream_t st, const FtDeliverRec *recs, int nRecs, int maxWords, int parity);
 int ft_launch_build_grid_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxLevels, bool twoCam);
@@ -197,6 +198,14 @@ int ft_launch_search_last_batch(hipStream_t st, void *arena, const FtBatchJob *j
                                 int fReset, float th);
 int ft_launch_search_local_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxPoints, int pass, int fCur, int fPrev,
                                  int fReset, float th, float nnRatio);
+// Parts of the launches below whose kernels live in kernels_search.hip (the launches themselves: kernels_search_rows.hip): the
+// projections of the last-frame points in front of ft_launch_search_last_first, and the general kernel on the slow lists behind the
+// lean kernel of ft_launch_search_*_batch_lean
+int ft_launch_last_project_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxPoints);
+int ft_launch_search_last_batch_slow(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int pass, int fCur, int fPrev, int fReset,
+                                     float th);
+int ft_launch_search_local_batch_slow(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int pass, int fCur, int fPrev, int fReset,
+                                      float th, float nnRatio);
 // the first pass with four points per wave (a point = a row of 16 lanes): every frame needs its grid and the candidate cache;
 // fills the lists, results and writer table exactly as pass 0 of ft_launch_search_*_batch does
 int ft_launch_search_last_first(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxPoints, float th);
@@ -294,7 +303,7 @@ __device__ __forceinline__ Window cell_window(const FtDevFrame &F, float x, floa
     return w;
 }
 
-// Re-derives a pointer read from a job record from the arena pointer the kernel got as an argument (kernels_search.hip: a
+// Re-derives a pointer read from a job record from the arena pointer the kernel got as an argument (FramePtrs, search_dev.h: a
 // pointer out of memory is a generic pointer to the compiler): arena + (p - address of the arena, passed as an integer)
 struct Rebase {
     uint8_t *arena;
@@ -304,4 +313,6 @@ struct Rebase {
         return p ? (T *)(arena + ((unsigned long long)p - addr)) : nullptr;
     }
 };
+// (host: what every launch of a batch passes for its arena)
+inline Rebase rebase_of(void *arena) { return Rebase{(uint8_t *)arena, (unsigned long long)(uintptr_t)arena}; }
 #endif

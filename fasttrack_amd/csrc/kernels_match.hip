@@ -22,10 +22,6 @@ __device__ __forceinline__ const uint8_t *level_ptr(const FtGeom &g, int level, 
     return pyr + (size_t)slot * g.pyrPerSlot + g.lv[level].off;
 }
 
-__device__ __forceinline__ int hamming256(const unsigned long long a[4], const unsigned long long *b) {
-    return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);
-}
-
 // One wave per left keypoint.
 __global__ __launch_bounds__(256) void k_stereo_match(FtGeom g, const uint8_t *const *l0L, const uint8_t *const *l0R,
                                                       int l0pitchL, int l0pitchR, const uint8_t *pyrL,

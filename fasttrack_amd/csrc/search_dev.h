@@ -1,0 +1,245 @@
+// Device side of the projection searches: what more than one of kernels_search.hip, kernels_search_rows.hip,
+// kernels_resolve.hip and kernels_frame.hip uses - a frame's pointers, the candidate key, the claim records of a pass, the
+// meta word of a candidate list, a window's entry, the camera models.  A helper that only one of those files uses lives in
+// that file.  Everything here is __device__ __forceinline__ (or a type) in an anonymous namespace: nothing links across files.
+// Device only: nothing includes this header except those four .hip files.
+#pragma once
+#include "kb8_math.h"
+#include "ft_search.h"
+#include "wave_ops.h"
+
+namespace {
+
+// The array pointers of a frame as the scans use them.  The kernels of ONE frame get the frame as a kernel argument and
+// its pointers are global pointers to the compiler; a pointer read from a record in memory (the job records of the batch
+// kernels, FtBatchJob) is a GENERIC pointer - flat_load: both wait counters, an aperture check per access - and neither
+// a cast through the global address space nor llvm.assume(!is_shared && !is_private) survives the optimiser.  What does:
+// re-deriving the pointer from a pointer that IS a kernel argument - the batch's device arena, with the arena's address
+// passed a second time as a plain integer, so that arena + (p - address) cannot be folded back into p.  Everything a job
+// record points to lies inside the arena of its batch (tracked_batch.cpp).
+struct NoRebase {  // the pointers are kernel arguments already
+    template <class T>
+    __device__ __forceinline__ T *operator()(T *p) const {
+        return p;
+    }
+};
+struct FramePtrs {
+    const ft_keypoint *keys, *keysR;
+    const uint8_t *desc;
+    const float *uright;
+    const int *holderObs, *l2r, *r2l;
+    const int *gridStart[2];
+    const float4 *gridRec[2];
+    const uint8_t *gridDesc[2];
+};
+template <class RB>
+__device__ __forceinline__ FramePtrs frame_ptrs(const FtDevFrame &F, const RB &rb) {
+    FramePtrs Q;
+    Q.keys = rb(F.keys); Q.keysR = rb(F.keysR); Q.desc = rb(F.desc); Q.uright = rb(F.uright);
+    Q.holderObs = rb(F.holderObs); Q.l2r = rb(F.l2r); Q.r2l = rb(F.r2l);
+    Q.gridStart[0] = rb(F.gridStart[0]); Q.gridStart[1] = rb(F.gridStart[1]);
+    Q.gridRec[0] = rb(F.gridRec[0]); Q.gridRec[1] = rb(F.gridRec[1]);
+    Q.gridDesc[0] = rb(F.gridDesc[0]); Q.gridDesc[1] = rb(F.gridDesc[1]);
+    return Q;
+}
+#define FT_NO_REBASE (NoRebase{})
+
+#define KEY_NONE 0xffffffffffffffffull
+// Candidate key: (distance, cell x, cell y, index) in the high bits - ascending keys are the scan order of the CPU loop, see
+// the header of kernels_search.hip - and below them what a later pass would otherwise have to fetch again through dependent loads: the keypoint's
+// octave (four bits: checkFrame, search_host.h, admits octaves of [0, nlevels) only; masked here so that the keypoints of a
+// BOUND frame, which no host check sees, can never spill into the index) and whether it was held before the call
+// (mvpMapPoints[idx]->Observations() > 0).  The index is unique inside a window, so the low bits never decide a comparison.
+__device__ __forceinline__ unsigned long long make_key(int dist, int cx, int cy, int idx, int octave, bool heldBefore) {
+    return ((unsigned long long)dist << 41) | ((unsigned long long)cx << 35) | ((unsigned long long)cy << 29) |
+           ((unsigned long long)idx << 5) | ((unsigned long long)(octave & 15) << 1) | (heldBefore ? 1ull : 0ull);
+}
+__device__ __forceinline__ int key_dist(unsigned long long k) { return (int)(k >> 41); }
+__device__ __forceinline__ int key_idx(unsigned long long k) { return (int)((k >> 5) & 0xffffffull); }
+__device__ __forceinline__ int key_octave(unsigned long long k) { return (int)((k >> 1) & 15ull); }
+__device__ __forceinline__ bool key_held(unsigned long long k) { return (k & 1ull) != 0; }
+
+// The words one pass of the claim iteration hands to the next - writer records, lists, results, flags - are written and read by
+// DIFFERENT workgroups, but of DIFFERENT launches: a pass reads what the previous launch wrote (its own L1 starts empty) and
+// writes what the next launch reads, never a word it also reads.  Plain loads and stores therefore do (rounds 3 - 4 kept them
+// agent-scope atomics, sc1, for the sake of the persistent single-launch form, deleted in round 5): a record is two 16-byte
+// loads that the L1 may keep for the other points of the CU that look at the same keypoint, a clear is 16-byte stores.  Only the
+// read-modify-writes are atomics (record positions, list heads, the "changed" flag).
+__device__ __forceinline__ int shared_load(const int *p) { return *p; }
+__device__ __forceinline__ void shared_store(int *p, int v) { *p = v; }
+
+// Writer table of a pass: per keypoint a 32-byte record {last position handed out, 7 entries}, entry = (4 * point + write
+// kind) << 1 | (Observations() of the point > 0), -1 = empty; an eighth and later writer of one keypoint (never seen outside
+// directed tests) goes to the overflow lists head / next, which hold the same entries.  One 32-byte read tells a later
+// pass everything about a keypoint - where the linked lists of rounds 1-3 cost a dependent load per writer plus one for the
+// writer's Observations() (a later pass is nothing but a chain of such round trips, ~1 us each).
+#define FT_TAB_ENTRIES 7
+// F.mvpMapPoints[kp] && ->Observations() > 0 as seen by map point i: the last writer j < i of the previous pass decides,
+// else the pre-call holder (heldBefore)
+struct LockRec {
+    unsigned long long a, b, c, d;
+};
+__device__ __forceinline__ LockRec lock_record(const FtClaims &C, int kp) {
+    const uint4 *rec = (const uint4 *)(C.tab + 8 * (size_t)kp);
+    const uint4 lo = rec[0], hi = rec[1];
+    LockRec r;
+    r.a = (unsigned long long)lo.x | ((unsigned long long)lo.y << 32);
+    r.b = (unsigned long long)lo.z | ((unsigned long long)lo.w << 32);
+    r.c = (unsigned long long)hi.x | ((unsigned long long)hi.y << 32);
+    r.d = (unsigned long long)hi.z | ((unsigned long long)hi.w << 32);
+    return r;
+}
+// the decision of is_locked on a record that is already in registers (not a first pass)
+__device__ __forceinline__ bool locked_by(const FtClaims &C, const LockRec &r, int kp, int i, bool heldBefore) {
+    const unsigned long long a = r.a, b = r.b, c = r.c, d = r.d;
+    const int last = (int)(unsigned)a;
+    int best = -1;
+    auto take = [&](int e) {
+        if (e >= 0 && (e >> 3) < i && e > best) best = e;
+    };
+    take((int)(a >> 32)); take((int)(unsigned)b); take((int)(b >> 32)); take((int)(unsigned)c);
+    take((int)(c >> 32)); take((int)(unsigned)d); take((int)(d >> 32));
+    if (last >= FT_TAB_ENTRIES)
+        for (int e = shared_load(&C.head[kp]); e >= 0; e = shared_load(&C.next[e >> 1])) take(e);
+    return best >= 0 ? (best & 1) != 0 : heldBefore;
+}
+__device__ __forceinline__ bool is_locked(const FtClaims &C, int kp, int i, bool heldBefore) {
+    if (C.firstPass) return heldBefore;
+    return locked_by(C, lock_record(C, kp), kp, i, heldBefore);
+}
+
+// start of a claim-iteration pass (see FtClaims): false = the iteration has converged, nothing to do
+// (blk of nblk: this workgroup among the frame's - the launch's own numbers unless the launcher laid the frames out itself)
+__device__ __forceinline__ bool claims_begin_pass(const FtClaims &C, int blk, int nblk) {
+    if (C.flagPrev && shared_load(C.flagPrev) == -1) {
+        // batch form, first pass of a later burst: the frame had converged before this burst began.  Its flag words of this
+        // burst's parity still hold what an earlier burst left there ("changed" for the passes it ran then): they all read
+        // "unchanged" from here on, so that every later pass of the burst returns here as well.
+        if (C.flagStick && blk == 0 && threadIdx.x < FT_BATCH_FLAGS / 2) shared_store(C.flagStick + threadIdx.x, -1);
+        return false;
+    }
+    const int t = blk * blockDim.x + threadIdx.x, T = nblk * blockDim.x;
+    for (int k = t; k < C.nKp; k += T) shared_store(&C.headClear[k], -1);
+    uint4 *tc = (uint4 *)C.tabClear;  // (32-byte records, 32-byte aligned)
+    for (int k = t; k < 2 * C.nKp; k += T) tc[k] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    if (t == 0) {
+        shared_store(C.flagReset, -1);
+        if (C.firstPass) shared_store(C.flagCur, 0);  // the first pass always "changes" its input
+    }
+    return true;
+}
+__device__ __forceinline__ bool claims_begin_pass(const FtClaims &C) { return claims_begin_pass(C, (int)blockIdx.x, (int)gridDim.x); }
+
+// ---- B frames per launch (ft_tracked_batch) --------------------------------------------------------------------------------
+// One frame at a time leaves the chip idle by construction: a pass of the claim iteration is ~500 workgroups and a handful
+// of dependent L2 round trips, 9 - 13 passes per search, each a launch.  Here blockIdx.y is the FRAME: everything a pass
+// needs of a frame - the frame itself, its points, its rotating claim buffers - sits in a job record in HBM (read through
+// scalar loads: the address is uniform), the pass number selects the buffers exactly as fixedPoint (search_host.h) does for a
+// launch of its own, and every frame has its own convergence flags, so that the workgroups of a frame whose iteration has
+// reached its fixed point return at once while the other frames go on: the batch runs max-over-frames passes.
+__device__ __forceinline__ FtClaims job_claims(const FtBatchJob &J, const Rebase &rb, int pass, int fCur, int fPrev, int fReset, int *&res) {
+    const size_t K = (size_t)J.K, R = (size_t)4 * J.nPoints;
+    int *head = rb(J.head), *tab = rb(J.tab), *next = rb(J.next), *resB = rb(J.res), *flags = rb(J.flags);
+    FtClaims C;
+    C.firstPass = pass == 0;
+    C.head = head + (size_t)(pass % 3) * K;
+    C.headWrite = head + (size_t)((pass + 1) % 3) * K;
+    C.headClear = head + (size_t)((pass + 2) % 3) * K;
+    C.tab = tab + (size_t)(pass % 3) * 8 * K;
+    C.tabWrite = tab + (size_t)((pass + 1) % 3) * 8 * K;
+    C.tabClear = tab + (size_t)((pass + 2) % 3) * 8 * K;
+    C.next = next + (size_t)((pass + 1) & 1) * R;
+    C.nextWrite = next + (size_t)(pass & 1) * R;
+    C.resPrev = resB + (size_t)((pass + 1) & 1) * R;
+    C.obs = rb(J.obs);
+    C.nKp = J.nKp;
+    C.flagCur = flags + fCur;
+    C.flagPrev = fPrev >= 0 ? flags + fPrev : nullptr;
+    C.flagReset = flags + fReset;
+    C.flagStick = (fPrev >= 0 && (fPrev / (FT_BATCH_FLAGS / 2)) != (fCur / (FT_BATCH_FLAGS / 2))) ? flags + (fCur & ~(FT_BATCH_FLAGS / 2 - 1)) : nullptr;
+    C.cache = rb(J.cache);
+    res = resB + (size_t)(pass & 1) * R;
+    return C;
+}
+
+__device__ __forceinline__ unsigned div_magic_u(int d) { return d > 1 ? 0xffffffffu / (unsigned)d + 1u : 0u; }
+
+// key joins the two smallest keys seen (k0 <= k1), as selects: written as `if (key < k0) { k1 = k0; k0 = key; } else if
+// (key < k1) k1 = key;` inside the window lambda the compiler selects between the ADDRESSES of k0 and k1 and keeps both in
+// scratch memory - a load and a store per candidate
+__device__ __forceinline__ void two_min_insert(unsigned long long &k0, unsigned long long &k1, unsigned long long key) {
+    const unsigned long long larger = key < k0 ? k0 : key;
+    k0 = key < k0 ? key : k0;
+    k1 = larger < k1 ? larger : k1;
+}
+
+// ---- candidate cache of the claim iteration (FtClaims::cache): the meta word of a list ----
+// (the lists are filed by the first pass that reaches a (point, camera) window: cache_append / cache_end in kernels_search.hip,
+// row_cache_append / row_cache_end in kernels_search_rows.hip)
+// The best candidates first.  A later pass needs the smallest (two smallest) UNLOCKED keys of a list, and a key's order is
+// its distance before anything else: with the keys of the FT_CACHE_HEAD (or a few more) smallest distances at the front of
+// the list, a pass that finds enough unlocked keys among them need not look at the rest - at th 15 a window holds ~190
+// candidates, and every candidate looked at is a 32-byte record read.  A kernel of its own does it once behind the first pass
+// of a batch (k_cache_partition_batch; inside the search kernels it cost them 45 registers): the smallest distance D with at
+// least FT_CACHE_HEAD keys <= D by bisection over the 9 bits of the distance (a count per step), then a stable partition of
+// the list by dist <= D.  The head's length goes into the meta word; a list that is short, or whose head would not be short
+// (many equal distances), keeps head = count - as every list of the single-frame path does.
+#ifndef FT_CACHE_HEAD
+#define FT_CACHE_HEAD 16
+#endif
+#ifndef FT_CACHE_HEAD_MAX
+#define FT_CACHE_HEAD_MAX 48
+#endif
+// length of the list's head (cache_partition): <= the count
+__device__ __forceinline__ int cache_head(unsigned long long meta) { return (int)((meta >> 40) & 0x3ffull); }
+// 0 = not built yet, 1 = usable (count = candidates filed), 2 = built but too many candidates: scan the window again
+__device__ __forceinline__ int cache_state_of(unsigned long long meta, int &count, bool &anyInBox) {
+    count = 0;
+    anyInBox = false;
+    if (meta == KEY_NONE) return 0;
+    count = (int)(unsigned)meta;
+    anyInBox = ((meta >> 32) & 1ull) != 0;
+    return count <= FT_CACHE_CAP ? 1 : 2;
+}
+
+// A keypoint of a window as the scans see it: position, octave, uright, descriptor - from the search records of the grid
+// (one 16-byte and one 32-byte read at the entry's position) or, without a grid, from the frame's own arrays.
+struct WinEntry {
+    float x, y, uright;  // uright: < 0 = none (or a two-camera frame)
+    int idx, octave, cx, cy;
+    unsigned long long d[4];
+};
+// level band and box test of GetFeaturesInArea for a keypoint whose cell is already known to lie in the window
+__device__ __forceinline__ bool in_box(const WinEntry &kp, float x, float y, float r, int minLevel, int maxLevel) {
+    const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
+    if (checkLevels) {
+        if (kp.octave < minLevel) return false;
+        if (maxLevel >= 0 && kp.octave > maxLevel) return false;
+    }
+    const float dx = __fsub_rn(kp.x, x), dy = __fsub_rn(kp.y, y);
+    return fabsf(dx) < r && fabsf(dy) < r;
+}
+
+// camera models: src/CameraModels/Pinhole.cpp:43-49, KannalaBrandt8.cpp:67-84
+__device__ __forceinline__ void project_cam(const FtDevFrame &F, const float p[3], float uv[2]) {
+    if (F.camModel == 0) {
+        uv[0] = __fadd_rn(__fdiv_rn(__fmul_rn(F.cam[0], p[0]), p[2]), F.cam[2]);
+        uv[1] = __fadd_rn(__fdiv_rn(__fmul_rn(F.cam[1], p[1]), p[2]), F.cam[3]);
+    } else {
+        const float x2y2 = __fadd_rn(__fmul_rn(p[0], p[0]), __fmul_rn(p[1], p[1]));
+        const float theta = ft_atan2_f(sqrtf(x2y2), p[2]);
+        const float psi = ft_atan2_f(p[1], p[0]);
+        const float t2 = __fmul_rn(theta, theta);
+        const float t3 = __fmul_rn(theta, t2);
+        const float t5 = __fmul_rn(t3, t2);
+        const float t7 = __fmul_rn(t5, t2);
+        const float t9 = __fmul_rn(t7, t2);
+        const float r = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(theta, __fmul_rn(F.cam[4], t3)), __fmul_rn(F.cam[5], t5)),
+                                            __fmul_rn(F.cam[6], t7)),
+                                  __fmul_rn(F.cam[7], t9));
+        uv[0] = __fadd_rn(__fmul_rn(__fmul_rn(F.cam[0], r), ft_cos_f(psi)), F.cam[2]);
+        uv[1] = __fadd_rn(__fmul_rn(__fmul_rn(F.cam[1], r), ft_sin_f(psi)), F.cam[3]);
+    }
+}
+
+}  // namespace

@@ -2,8 +2,8 @@
 // tracked_frame.cpp, init_search.cpp, tracked_batch.cpp): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
 // (reference include/Kernels/KernelController.h:40-46) together with the acceptance loops the reference keeps in the caller
 // (src/ORBmatcher.cc:241-308, 2013-2081).  Windowing, level/box tests and every Hamming distance run on the device
-// (kernels_search.hip); the host only marshals arrays, drives the fixed-point passes and replays the O(M) write list in map
-// point order to produce mvpMapPoints / the rotation histogram, exactly as the reference's caller does.
+// (kernels_search*.hip, kernels_resolve.hip, kernels_frame.hip); the host only marshals arrays, drives the fixed-point passes and
+// replays the O(M) write list in map point order to produce mvpMapPoints / the rotation histogram, exactly as the reference's caller does.
 // Host only: no kernel includes this header.
 #pragma once
 #include <algorithm>
@@ -45,7 +45,7 @@ inline int checkFrame(const ft_frame_view *F) {
     FT_REQUIRE(F->Nleft == -1 || (F->left_to_right && F->right_to_left), "stereo match tables are null");
     FT_REQUIRE(F->scale_factors && F->nlevels >= 1 && F->nlevels <= FT_MAX_LEVELS, "scale factors missing");
     FT_REQUIRE(F->cam_model == 0 || F->cam_model == 1, "unknown camera model");
-    // the searches read a keypoint's octave back from four bits of a candidate key (make_key, kernels_search.hip)
+    // the searches read a keypoint's octave back from four bits of a candidate key (make_key, search_dev.h)
     const int nL = F->Nleft == -1 ? F->N : F->Nleft, nR = F->Nleft == -1 ? 0 : F->N - F->Nleft;
     for (int i = 0; i < nL; i++) FT_REQUIRE(F->keys[i].octave >= 0 && F->keys[i].octave < F->nlevels, "keypoint octave outside [0, nlevels)");
     for (int i = 0; i < nR; i++)

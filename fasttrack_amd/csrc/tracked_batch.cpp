@@ -6,7 +6,7 @@
 // (blockIdx.y = frame, per-frame convergence flags; the batch runs max-over-frames passes).  Results per frame are those of
 // ft_tracked_frame_* on that frame, bit for bit.
 //
-// Memory: ONE device arena per batch (the kernels re-derive every pointer of a job record from it: Rebase, kernels_search.hip)
+// Memory: ONE device arena per batch (the kernels re-derive every pointer of a job record from it: Rebase, ft_search.h; FramePtrs, search_dev.h)
 //   work   | per call: job records, delivery records, the frames' point arrays (compact), frustum outputs
 //   frames | keypoints, descriptors, uright, match tables, holder_obs of the uploaded frames (compact)
 //   flags  | 32 words per frame;  counts | 1 word per frame (isInFrustum's nToMatch)

@@ -1,4 +1,5 @@
-// Device helpers shared by the gfx950 kernels (wave64): explicit global loads, 24-bit multiplies, DPP reductions.
+// Device helpers shared by the gfx950 kernels (wave64): explicit global loads, 24-bit multiplies, DPP reductions, the Hamming
+// distance of two descriptors.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,6 +84,11 @@ __device__ __forceinline__ int row_max_i32(int v) {
     v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));
     v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));
     return v;
+}
+
+// ORBmatcher::DescriptorDistance (reference src/ORBmatcher.cc:2256-2272) of two 256-bit descriptors as 4 x uint64
+__device__ __forceinline__ int hamming256(const unsigned long long a[4], const unsigned long long *b) {
+    return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);
 }
 
 // Low 32 bits of the product of two operands that fit 24 bits, as ONE full-rate instruction.  (__mul24 is dissolved

@@ -220,7 +220,7 @@ def test_option_text_in_the_environment_must_be_an_integer(bad):
 
 def test_library_is_not_built_with_threadgroup_split():
     """k_resolve_batch orders a chunk's atomics before the next chunk's loads through ONE CU's in-order vector-memory path
-    (kernels_search.hip): the kernel descriptors the Makefile's flags produce must say tg_split 0, and the Makefile refuses
+    (kernels_resolve.hip): the kernel descriptors the Makefile's flags produce must say tg_split 0, and the Makefile refuses
     -mtgsplit"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "fasttrack_amd", "csrc")

@@ -38,11 +38,11 @@ KERNELS = [
     ("kernels_extract.hip", "9k_compactE", "k_compact"),
     ("kernels_octree.hip", "8k_octreeE", "k_octree"),
     ("kernels_match.hip", "14k_stereo_matchE", "k_stereo_match"),
-    ("kernels_search.hip", "19k_fisheye_2nn_batchE", "k_fisheye_2nn_batch"),
-    ("kernels_search.hip", "15k_resolve_batchILb0ELb1EE", "k_resolve_batch<false>"),
-    ("kernels_search.hip", "15k_resolve_batchILb1ELb1EE", "k_resolve_batch<true>"),
-    ("kernels_search.hip", "19k_search_last_firstE", "k_search_last_first"),
-    ("kernels_search.hip", "20k_search_local_firstE", "k_search_local_first"),
+    ("kernels_frame.hip", "19k_fisheye_2nn_batchE", "k_fisheye_2nn_batch"),
+    ("kernels_resolve.hip", "15k_resolve_batchILb0ELb1EE", "k_resolve_batch<false>"),
+    ("kernels_resolve.hip", "15k_resolve_batchILb1ELb1EE", "k_resolve_batch<true>"),
+    ("kernels_search_rows.hip", "19k_search_last_firstE", "k_search_last_first"),
+    ("kernels_search_rows.hip", "20k_search_local_firstE", "k_search_local_first"),
 ]
 
 
