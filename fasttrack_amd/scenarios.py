@@ -11,6 +11,85 @@ def frame_bounds(width, height):
     return (0.0, 0.0, float(width), float(height))
 
 
+def GEOMETRY_BOUNDS(width, height):
+    """Image bounds other than (0, 0, w, h), all with fractional parts (Frame::ComputeImageBounds of a distorted camera):
+    loose = the undistorted corners of a barrel-distorted camera (bounds wider than the image), tight = bounds inside the
+    image, so that keypoints fall outside the 64x48 grid, edge = bounds on the extractor's own 19 px border."""
+    w, h = float(width), float(height)
+    return dict(loose=(-31.37, -22.81, w + 28.64, h + 19.23), tight=(41.3, 33.7, w - 37.6, h - 29.2),
+                edge=(19.0, 19.0, w - 19.0, h - 19.0))
+
+
+def grid_cells(keys, bounds, cols=64, rows=48):
+    """Frame::PosInGrid in its float32 arithmetic: cell = round((x - mnMinX) * mfGridElementWidthInv) with
+    mfGridElementWidthInv = float(FRAME_GRID_COLS) / float(mnMaxX - mnMinX) (Frame.cc:184-185, :749-759); round() is half away
+    from zero.  -> (cx, cy, outside): int32 cells and the keypoints PosInGrid rejects."""
+    minx, miny, maxx, maxy = [np.float32(v) for v in bounds]
+    inv_w = np.float32(cols) / np.float32(maxx - minx)
+    inv_h = np.float32(rows) / np.float32(maxy - miny)
+
+    def cell(v, lo, inv):
+        t = ((np.asarray(v, np.float32) - lo) * inv).astype(np.float32)
+        return (np.sign(t) * np.floor(np.abs(t).astype(np.float64) + 0.5)).astype(np.int32)
+    cx, cy = cell(keys["x"], minx, inv_w), cell(keys["y"], miny, inv_h)
+    outside = (cx < 0) | (cx >= cols) | (cy < 0) | (cy >= rows)
+    return cx, cy, outside
+
+
+LATTICE_KP = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
+                       ("class_id", "<i4")])   # cv::KeyPoint as the library and the oracle lay it out
+
+
+# tight-style bounds for the lattice: its first column and row land in grid column / row 0, and the cell windows of those keypoints
+# reach below cell 0 (floor((40 - 38.5 - 2) * inv) = -1: the clamp decides)
+LATTICE_SHIFTED_BOUNDS = (38.5, 37.5, 640.0 - 37.6, 480.0 - 29.2)
+
+
+def lattice_last_frame(spec, doubles=(), bounds=None, seed=0, unmatched=False, width=640, height=480):
+    """A directed frame for the rotation-consistency filter of SearchByProjection(CurrentFrame, LastFrame), no extraction:
+    keypoints on a 24 px lattice starting at (40, 40), 24 per row (17 rows in 640x480), octave 0, angle 0, random distinct
+    descriptors; a pinhole camera fx = fy = 400, cx, cy = 320, 240; last-frame points = keypoints back-projected at z = 5 with
+    the identity pose, carrying the keypoint's descriptor, octave 0 and angle = 30 degrees x bin.  Searched with th 2 every
+    window holds exactly one keypoint, so the rotation histogram of the search is `spec` itself.
+    spec: {bin: count} (a bin may be fractional: -0.01 / 30 is an angle of -0.01 degrees); every point gets a keypoint of its
+    own, keypoints dealt out in a seeded random order.  doubles: [(bin_first, bin_second)] - two consecutive points on ONE further
+    keypoint, the first with observations == 0, so the second is not blocked and overwrites it.  unmatched: the points carry the
+    complement of the descriptors (distance 256: nothing is accepted).
+    -> dict(keys, descriptors, bounds, cam, scale_factors, last, Tcw, kp_of_point, bin_of_point)"""
+    rng = np.random.default_rng(seed)
+    per_row, nrows = 24, (height - 80) // 24 + 1
+    n = per_row * nrows
+    keys = np.zeros(n, LATTICE_KP)
+    keys["x"] = 40.0 + 24.0 * (np.arange(n) % per_row)
+    keys["y"] = 40.0 + 24.0 * (np.arange(n) // per_row)
+    keys["size"], keys["response"], keys["class_id"] = 31.0, 50.0, -1
+    while True:
+        desc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        if len(np.unique(desc, axis=0)) == n:
+            break
+    bins = [b for b, c in spec.items() for _ in range(c)]
+    n_pts, n_kp = len(bins) + 2 * len(doubles), len(bins) + len(doubles)
+    assert n_kp <= n, "more points than lattice keypoints"
+    order = rng.permutation(n)[:n_kp]
+    kp_of_point = np.concatenate([order[:len(bins)], np.repeat(order[len(bins):], 2)]).astype(np.int32)
+    bin_of_point = np.array(bins + [b for d in doubles for b in d], np.float64)
+    obs = (1 + np.arange(n_pts) % 5).astype(np.int32)
+    obs[len(bins)::2] = 0            # the first point of a double holds its keypoint without blocking it
+    fx = fy = np.float32(400.0)
+    cx, cy, z = np.float32(320.0), np.float32(240.0), np.float32(5.0)
+    kx, ky = keys["x"][kp_of_point], keys["y"][kp_of_point]
+    world = np.stack([(kx - cx) / fx * z, (ky - cy) / fy * z, np.full(n_pts, z, np.float32)], 1).astype(np.float32)
+    d = desc[kp_of_point]
+    sf = np.ones(8, np.float32)
+    for l in range(1, 8):   # ORBextractor's table: mvScaleFactor[i] = mvScaleFactor[i - 1] * scaleFactor, in float
+        sf[l] = sf[l - 1] * np.float32(1.2)
+    last = dict(valid=np.ones(n_pts, np.uint8), world_pos=world.reshape(n_pts, 3), descriptors=(~d if unmatched else d.copy()),
+                observations=obs, octave=np.zeros(n_pts, np.int32), angle=(30.0 * bin_of_point).astype(np.float32))
+    return dict(keys=keys, descriptors=desc, bounds=frame_bounds(width, height) if bounds is None else tuple(bounds),
+                cam=[400.0, 400.0, 320.0, 240.0], scale_factors=sf, last=last,
+                Tcw=np.eye(3, 4, dtype=np.float32), kp_of_point=kp_of_point, bin_of_point=bin_of_point)
+
+
 
 def random_pose(rng, trans=0.05, rot=0.01):
     """small SE(3) step as a row-major 3x4 float32 matrix"""

@@ -7,7 +7,10 @@ compares every frame's assignments, frustum fields, nToMatch and final holder_ob
 A trial runs under search_cache 3 (one-launch resolution, k_resolve_batch), 2 (the same for 24 frames and more) or 1 (claim passes)
 and a random burst length; 5 % of the
 trials use windows so wide that candidate lists outgrow the cache (resolution falls back to the passes for those frames).
-usage: tests/tools/soak_batch.py [--trials N] [--seed S] [--frames B]      exit code 1 on any mismatch"""
+--geometry draws image bounds (every side of the image rectangle moved by up to 45 px, fractional) and a number of pyramid levels
+(1 - 12) per frame and a pyramid factor (1.1 / 1.2 / 1.5 / 2.0: one log scale factor serves a track_local_map call) per trial, from a
+generator of its own: without the flag the trial stream is what it always was.
+usage: tests/tools/soak_batch.py [--trials N] [--seed S] [--frames B] [--geometry]      exit code 1 on any mismatch"""
 import argparse
 import os
 import sys
@@ -22,7 +25,6 @@ from fasttrack_amd import orb, synth  # noqa: E402
 from oracle import binding as ob  # noqa: E402
 import scenarios as sc  # noqa: E402
 
-LOG_SF = float(np.float32(np.log(np.float32(1.2))))
 TRL = np.concatenate([np.eye(3), [[-0.101], [0.0], [0.0]]], 1).astype(np.float32)
 TLR = (0.101, 0.0, 0.0)
 
@@ -32,8 +34,10 @@ def main(argv=None):
     ap.add_argument("--trials", type=int, default=20)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--geometry", action="store_true", help="random image bounds and pyramid depth per frame, pyramid factor per trial")
     args = ap.parse_args(argv)
     rng = np.random.default_rng(args.seed)
+    grng = np.random.default_rng([args.seed, 0x6e0])   # the geometry's own stream: the trials themselves stay what they were
     ctx = orb.Context(0)
     sf, _ = ob.scale_factors(1.2, 8)
     B = args.frames
@@ -43,13 +47,16 @@ def main(argv=None):
     t0 = time.time()
     bases = {}
 
-    def base(kind, w, h, nf, seed):
-        key = (kind, w, h, nf, seed)
+    def base(kind, w, h, nf, seed, factor=1.2, nlevels=8):
+        key = (kind, w, h, nf, seed, factor, nlevels)
         if key not in bases:
             if len(bases) > 24:
                 bases.pop(next(iter(bases)))
-            fr = sc.fisheye_frame_scenario(w, h, nf, seed) if kind == 1 else sc.oracle_stereo_frame(w, h, nf, seed)
-            if kind == 0:
+            if args.geometry:
+                fr = sc.geometry_frame(w, h, nf, seed, factor, nlevels, two_cameras=kind == 1, cache=False)
+            else:
+                fr = sc.fisheye_frame_scenario(w, h, nf, seed) if kind == 1 else sc.oracle_stereo_frame(w, h, nf, seed)
+            if kind == 0 and "sm" not in fr:
                 fr["sm"] = ob.stereo_match(fr["exL"], fr["exR"], fr["kL"], fr["kR"], fr["dL"], fr["dR"], fr["intr"]["mbf"], fr["intr"]["mb"])
             bases[key] = fr
         return bases[key]
@@ -60,11 +67,19 @@ def main(argv=None):
         th_far = float(rng.uniform(4, 12))
         nn = float(rng.choice([0.8, 0.6, 0.9]))
         views, lasts, Tcws, ptss, poses, orc = [], [], [], [], [], []
+        factor = float(grng.choice([1.1, 1.2, 1.5, 2.0])) if args.geometry else 1.2
+        log_sf = float(np.float32(np.log(np.float32(factor))))
         for f in range(B):
             kind = int(rng.random() < 0.6)
             w, h = (512, 512) if kind == 1 else [(752, 480), (640, 480), (376, 240)][int(rng.integers(0, 3))]
             nf = int(rng.choice([500, 1000, 1500, 2000]))
-            fr = base(kind, w, h, nf, int(rng.integers(0, 6)))
+            bounds, nlev = sc.frame_bounds(w, h), 8
+            if args.geometry:
+                bounds, _, nlev = sc.random_geometry(grng, w, h)
+                while nlev > 1 and min(w, h) / factor ** (nlev - 1) < 96:   # (random_geometry sized it for its own factor)
+                    nlev -= 1
+                sf, _ = ob.scale_factors(factor, nlev)
+            fr = base(kind, w, h, nf, int(rng.integers(0, 6)), factor, nlev)
             nl = max(int(len(fr["kL"]) * rng.uniform(0.4, 1.0)), 1) if rng.random() < 0.3 else len(fr["kL"])
             kL, dL = fr["kL"][:nl], fr["dL"][:nl]
             holder = np.where(rng.random(nl) < 0.1, rng.integers(0, 3, nl), -1).astype(np.int32)
@@ -73,25 +88,25 @@ def main(argv=None):
                 l2r = np.where(fr["l2r"][:nl] < nr, fr["l2r"][:nl], -1).astype(np.int32)
                 r2l = np.where(fr["r2l"] < nl, fr["r2l"], -1).astype(np.int32)
                 hold = np.concatenate([holder, np.full(nr, -1, np.int32)])
-                kw = dict(keys=kL, keys_right=fr["kR"], descriptors=np.concatenate([dL, fr["dR"]]), bounds=sc.frame_bounds(w, h),
+                kw = dict(keys=kL, keys_right=fr["kR"], descriptors=np.concatenate([dL, fr["dR"]]), bounds=bounds,
                           left_to_right=l2r, right_to_left=r2l, cam_model=1, cam=list(sc.KB8_CAM), Trl=TRL, holder_obs=hold)
                 intr = dict(fx=sc.KB8_CAM[0], fy=sc.KB8_CAM[1], cx=sc.KB8_CAM[2], cy=sc.KB8_CAM[3])
                 depth, uright, tlr = np.zeros(nl, np.float32), None, TLR
             else:
                 uright, depth, intr, tlr = fr["sm"]["uright"][:nl], fr["sm"]["depth"][:nl], fr["intr"], (0, 0, 0)
-                kw = dict(keys=kL, descriptors=dL, bounds=sc.frame_bounds(w, h), mbf=intr["mbf"], mb=intr["mb"], uright=uright,
+                kw = dict(keys=kL, descriptors=dL, bounds=bounds, mbf=intr["mbf"], mb=intr["mb"], uright=uright,
                           holder_obs=holder, cam=[intr[k] for k in ("fx", "fy", "cx", "cy")])
             oF, gF = ob.FrameView(scale_factors_=sf, **kw), orb.FrameView(scale_factors=sf, **kw)
             seed = int(rng.integers(0, 1 << 30))
             last, Tcw = sc.last_frame_scenario(kL, dL, uright, depth, intr, w, h, seed=seed)
             M = int(rng.integers(0, 2001))
-            pts, Rcw, tcw = sc.map_points_scenario(kL, dL, depth, intr, 8, sf, seed + 1, M=max(M, 1))
+            pts, Rcw, tcw = sc.map_points_scenario(kL, dL, depth, intr, nlev, sf, seed + 1, M=max(M, 1))
             if M == 0:
                 pts = {k: v[:0] for k, v in pts.items()}
             if rng.random() < 0.05:
                 last = {k: v[:0] for k, v in last.items()}
             o1 = ob.search_last_frame(oF, last, Tcw, th, False, False, True)
-            ofr = ob.is_in_frustum(oF, ob.make_pose(Rcw, tcw, tlr), pts, 0.5, LOG_SF)
+            ofr = ob.is_in_frustum(oF, ob.make_pose(Rcw, tcw, tlr), pts, 0.5, log_sf)
             o2 = ob.search_local_points(oF, sc.local_points_from_frustum(ofr, pts, far, th_far), th, nn)
             views.append(gF); lasts.append(last); Tcws.append(Tcw); ptss.append(pts); poses.append(orb.make_pose(Rcw, tcw, tlr))
             orc.append((o1, ofr, o2, oF))
@@ -107,11 +122,11 @@ def main(argv=None):
             if split:
                 tb.search_last_frame(pl1, th=th, submit=True)
                 g1 = tb.wait()
-                tb.track_local_map(pl2, viewing_cos_limit=0.5, log_scale_factor=LOG_SF, th=th, nn_ratio=nn, far_points=far, th_far_points=th_far, submit=True)
+                tb.track_local_map(pl2, viewing_cos_limit=0.5, log_scale_factor=log_sf, th=th, nn_ratio=nn, far_points=far, th_far_points=th_far, submit=True)
                 g2 = tb.wait()
             else:
                 g1 = tb.search_last_frame(pl1, th=th)
-                g2 = tb.track_local_map(pl2, viewing_cos_limit=0.5, log_scale_factor=LOG_SF, th=th, nn_ratio=nn, far_points=far, th_far_points=th_far)
+                g2 = tb.track_local_map(pl2, viewing_cos_limit=0.5, log_scale_factor=log_sf, th=th, nn_ratio=nn, far_points=far, th_far_points=th_far)
         modes[opts["search_cache"]] += 1
         for f in range(B):
             o1, ofr, o2, oF = orc[f]

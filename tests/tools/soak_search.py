@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Long randomized parity run of the projection searches on an MI355X (not part of the test suite): both
 ORBmatcher::SearchByProjection overloads, Frame::isInFrustum and the resident tracked frame against the oracle.
-usage: tests/tools/soak_search.py [--trials N] [--seed S]
+usage: tests/tools/soak_search.py [--trials N] [--seed S] [--geometry]
 
 A trial draws a frame (size, feature count, scene kind; every fourth one a two-camera fisheye frame), extracts it with the
 oracle, and then runs several searches on it, each with its own random point set, window factor, flags and occupancy of
 mvpMapPoints: the one-shot kernel-controller calls and the sequence on a resident frame (search last frame -> frustum ->
 local map, holder_obs carried over).  Assignments, every raw array, the frustum fields and the final occupancy must equal
 the oracle's.  The two-camera trials add the KannalaBrandt8 model: a last-frame search and isInFrustum projecting through it
-and the fisheye stereo triangulation on a random rig, every output compared for equality.  Prints one line per failure and a summary; exit code 1 on any mismatch."""
+and the fisheye stereo triangulation on a random rig, every output compared for equality.  --geometry draws image bounds (every
+side of the image rectangle moved by up to 45 px, fractional) and a pyramid (factor 1.1 / 1.2 / 1.5 / 2.0, 1 - 12 levels) per trial,
+from a generator of its own: without the flag the trial stream is what it always was.  Prints one line per failure and a summary; exit code 1 on any mismatch."""
 import argparse
 import os
 import sys
@@ -23,26 +25,25 @@ from fasttrack_amd import orb, synth  # noqa: E402
 from oracle import binding as ob  # noqa: E402
 import scenarios as sc  # noqa: E402
 
-LOG_SF = float(np.float32(np.log(np.float32(1.2))))
 RAW1 = ("best_dist", "best_dist2", "best_level", "best_level2", "best_idx")
 RAW2 = RAW1 + ("best_dist_r", "best_dist2_r", "best_level_r", "best_level2_r", "best_idx_r")
 
 
-def frame_of(rng, w, h, nf, kind, seed):
+def frame_of(rng, w, h, nf, kind, seed, factor=1.2, nlevels=8):
     if kind == 0:
         L, R = synth.make_stereo_pair(w, h, seed)
     elif kind == 1:
         L, R = synth.make_planes_pair(w, h, seed=seed)
     else:
         L, R = synth.make_mosaic_pair(w, h, seed=seed, block=int(rng.integers(8, 20)))
-    exL, exR = ob.Extractor(nf), ob.Extractor(nf)
+    exL, exR = ob.Extractor(nf, factor, nlevels), ob.Extractor(nf, factor, nlevels)
     kL, dL, _ = exL.extract(L)
     kR, dR, _ = exR.extract(R)
     return dict(L=L, R=R, exL=exL, exR=exR, kL=kL, dL=dL, kR=kR, dR=dR, intr=synth.intrinsics(w, h))
 
 
-def views(fr, sf, w, h, uright, holder):
-    args = dict(keys=fr["kL"], descriptors=fr["dL"], bounds=sc.frame_bounds(w, h), mbf=fr["intr"]["mbf"], mb=fr["intr"]["mb"],
+def views(fr, sf, bounds, uright, holder):
+    args = dict(keys=fr["kL"], descriptors=fr["dL"], bounds=bounds, mbf=fr["intr"]["mbf"], mb=fr["intr"]["mb"],
                 uright=uright, holder_obs=holder, cam=[fr["intr"][k] for k in ("fx", "fy", "cx", "cy")])
     return ob.FrameView(scale_factors_=sf, **args), orb.FrameView(scale_factors=sf, **args)
 
@@ -60,10 +61,12 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=50)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--geometry", action="store_true", help="random image bounds and pyramid shape per trial")
     args = ap.parse_args(argv)
     rng = np.random.default_rng(args.seed)
+    grng = np.random.default_rng([args.seed, 0x6e0])   # the geometry's own stream: the trials themselves stay what they were
     ctx = orb.Context(0)
-    sf, _ = ob.scale_factors(1.2, 8)
+    sf8, _ = ob.scale_factors(1.2, 8)
     sizes = [(752, 480), (640, 480), (512, 512), (1280, 720), (376, 240)]
     fails, searches, matched, t0 = 0, 0, 0, time.time()
     kb8_frustum_points = kb8_pairs = se3_searches = 0
@@ -79,9 +82,12 @@ def main(argv=None):
         nf = int(rng.integers(300, 2001))
         seed = int(rng.integers(0, 1 << 30))
         two_cam = t % 4 == 3
-        desc = f"{w}x{h} nf{nf} seed{seed}"
+        bounds, factor, nl = sc.random_geometry(grng, w, h) if args.geometry else (sc.frame_bounds(w, h), 1.2, 8)
+        sf, _ = ob.scale_factors(factor, nl)
+        log_sf = float(np.float32(np.log(np.float32(factor))))
+        desc = f"{w}x{h} nf{nf} seed{seed}" + (f" bounds{tuple(round(b, 2) for b in bounds)} pyramid{factor}/{nl}" if args.geometry else "")
         if two_cam:
-            fr = frame_of(rng, w, h, nf, 0, seed)
+            fr = frame_of(rng, w, h, nf, 0, seed, factor, nl)
             m = ob.fisheye_match(fr["dL"], fr["dR"])
             l2r = m["matches"].astype(np.int32)
             r2l = np.full(len(fr["kR"]), -1, np.int32)
@@ -90,7 +96,7 @@ def main(argv=None):
             if len(fr["kL"]) < 8 or len(fr["kR"]) < 8:
                 continue
             kw = dict(keys=fr["kL"], keys_right=fr["kR"], descriptors=np.concatenate([fr["dL"], fr["dR"]]),
-                      bounds=sc.frame_bounds(w, h), left_to_right=l2r, right_to_left=r2l)
+                      bounds=bounds, left_to_right=l2r, right_to_left=r2l)
             for _ in range(3):
                 th = float(rng.choice([1.0, 3.0, 7.0, 15.0]))
                 pts = sc.two_camera_points(fr, sf, int(rng.integers(0, 1 << 30)), M=int(rng.integers(50, 3000)))
@@ -132,11 +138,11 @@ def main(argv=None):
             searches += 1
             matched += o["n"]
             intr = dict(fx=cam[0], fy=cam[1], cx=cam[2], cy=cam[3])
-            pts, Rcw, tcw = sc.map_points_scenario(fr["kL"], fr["dL"], np.zeros(N, np.float32), intr, 8, sf, int(rng.integers(0, 1 << 30)))
+            pts, Rcw, tcw = sc.map_points_scenario(fr["kL"], fr["dL"], np.zeros(N, np.float32), intr, nl, sf, int(rng.integers(0, 1 << 30)))
             tlr = (-float(Trl[0, 3]), 0.0, 0.0)
             oF, gF = ob.FrameView(scale_factors_=sf, **kwk), orb.FrameView(scale_factors=sf, **kwk)
-            ofr = ob.is_in_frustum(oF, ob.make_pose(Rcw, tcw, tlr), pts, 0.5, LOG_SF)
-            gfr = orb.is_in_frustum(ctx, gF, orb.make_pose(Rcw, tcw, tlr), pts, 0.5, LOG_SF)
+            ofr = ob.is_in_frustum(oF, ob.make_pose(Rcw, tcw, tlr), pts, 0.5, log_sf)
+            gfr = orb.is_in_frustum(ctx, gF, orb.make_pose(Rcw, tcw, tlr), pts, 0.5, log_sf)
             bad = next((k for k, _ in ob.FRUSTUM_FIELDS if not np.array_equal(gfr[k], ofr[k])), None)
             check(f"KB8 frustum [{desc}]", t, bad or (None if gfr["n"] == ofr["n"] else "n"))
             kb8_frustum_points += len(pts["world_pos"])
@@ -151,7 +157,7 @@ def main(argv=None):
             kL = np.zeros(n, ob.KP_DTYPE); kR = np.zeros(n, ob.KP_DTYPE)
             kL["x"], kL["y"], kL["octave"] = S["xy1"][:, 0], S["xy1"][:, 1], S["octave1"]
             kR["x"], kR["y"], kR["octave"] = S["xy2"][perm, 0], S["xy2"][perm, 1], S["octave2"][perm]
-            ls2 = (sf ** 2).astype(np.float32)
+            ls2 = (sf8 ** 2).astype(np.float32)   # (the rig scenario draws octaves 0 .. 7)
             o = ob.fisheye_stereo(ob.make_rig(sc.KB8_CAM, sc.KB8_CAM, S["Rlr"], S["tlr"]), dL, kL, dR, kR, ls2)
             g = orb.fisheye_stereo(ctx, sc.KB8_CAM, sc.KB8_CAM, S["Rlr"], S["tlr"], dL, kL, dR, kR, ls2)
             bad = next((k for k in ("matches", "depth", "p3d") if not np.array_equal(g[k], o[k])), None)
@@ -159,7 +165,7 @@ def main(argv=None):
             kb8_pairs += n
             continue
         kind = int(rng.integers(0, 3))
-        fr = frame_of(rng, w, h, nf, kind, seed)
+        fr = frame_of(rng, w, h, nf, kind, seed, factor, nl)
         N = len(fr["kL"])
         if N < 8:
             continue
@@ -172,7 +178,7 @@ def main(argv=None):
             holder = np.where(rng.random(N) < rng.uniform(0, 0.3), rng.integers(0, 3, N), -1).astype(np.int32)
             pts = sc.local_points_scenario(fr["kL"], fr["dL"], sf, w, h, seed=int(rng.integers(0, 1 << 30)), M=int(rng.integers(20, 4000)),
                                            uright=uright, dense=bool(rng.integers(0, 2)))
-            oF, gF = views(fr, sf, w, h, uright, holder)
+            oF, gF = views(fr, sf, bounds, uright, holder)
             o = ob.search_local_points(oF, pts, th)
             g = orb.KernelController.launchSearchLocalPointsKernel(ctx, gF, pts, th)
             check(f"local th{th} kind{kind} mono{int(mono)} [{desc}]", t, diff(g, o, RAW1) or
@@ -187,7 +193,7 @@ def main(argv=None):
         bwd = (not fwd) and bool(rng.random() < 0.2)
         ori = bool(rng.random() < 0.8)
         last, Tcw = sc.last_frame_scenario(fr["kL"], fr["dL"], sm["uright"], sm["depth"], fr["intr"], w, h, seed=int(rng.integers(0, 1 << 30)))
-        oF, gF = views(fr, sf, w, h, sm["uright"], None)
+        oF, gF = views(fr, sf, bounds, sm["uright"], None)
         if t % 2:  # every other trial hands the pose over as Sophus::SE3f holds it (the CPU branch's quaternion arithmetic)
             q, tt = sc.random_se3(rng, 0.03, 0.006)
             oT, gT = ob.SE3(q, tt), orb.SE3(q, tt)
@@ -201,19 +207,19 @@ def main(argv=None):
         searches += 1
         matched += o["n"]
         # --- the sequence on a resident frame ---
-        pts, Rcw, tcw = sc.map_points_scenario(fr["kL"], fr["dL"], sm["depth"], fr["intr"], 8, sf, int(rng.integers(0, 1 << 30)),
+        pts, Rcw, tcw = sc.map_points_scenario(fr["kL"], fr["dL"], sm["depth"], fr["intr"], nl, sf, int(rng.integers(0, 1 << 30)),
                                                M=int(rng.integers(100, 4000)))
         far = bool(rng.random() < 0.3)
         th_far = float(np.percentile(sm["depth"][sm["depth"] > 0], 85)) if far else 0.0
         th_last, th_local = float(rng.choice([7.0, 15.0])), float(rng.choice([1.0, 3.0, 5.0, 15.0]))
-        oF, gF = views(fr, sf, w, h, sm["uright"], None)
+        oF, gF = views(fr, sf, bounds, sm["uright"], None)
         o1 = ob.search_last_frame(oF, last, Tcw, th_last, False, False, True)
-        ofr = ob.is_in_frustum(oF, ob.make_pose(Rcw, tcw), pts, 0.5, LOG_SF)
+        ofr = ob.is_in_frustum(oF, ob.make_pose(Rcw, tcw), pts, 0.5, log_sf)
         o2 = ob.search_local_points(oF, sc.local_points_from_frustum(ofr, pts, far, th_far), th_local)
         tf = orb.TrackedFrame(ctx, max_keypoints=4096, max_points=4096)
         tf.upload(gF)
         g1 = tf.search_last_frame(last, Tcw, th_last)
-        g2 = tf.track_local_map(orb.make_pose(Rcw, tcw), pts, 0.5, LOG_SF, th_local, far_points=far, th_far_points=th_far)
+        g2 = tf.track_local_map(orb.make_pose(Rcw, tcw), pts, 0.5, log_sf, th_local, far_points=far, th_far_points=th_far)
         what = diff(g1, o1, ()) and "last: " + diff(g1, o1, ())
         if not what:
             for k, _ in ob.FRUSTUM_FIELDS:
