@@ -54,9 +54,10 @@ def _kb8_inputs(kL, dL, sf, seed, M):
     return last, Tcw, pts, Rcw, tcw
 
 
-def _check_frame(tag, g1, g2, gh, o1, ofr, o2, oF):
+def _check_frame(tag, g1, g2, gh, o1, ofr, o2, oF, frustum=True):
+    """frustum=False: a call that asked for no frustum fields (everything else is checked all the same)"""
     assert g1["n"] == o1["n"] and np.array_equal(g1["assign"], o1["assign"]), f"{tag}: last-frame search"
-    for k, _ in ob.FRUSTUM_FIELDS:
+    for k, _ in ob.FRUSTUM_FIELDS if frustum else ():
         assert np.array_equal(g2[k], ofr[k]), f"{tag}: frustum field {k}"
     assert g2["n_to_match"] == ofr["n"], f"{tag}: nToMatch"
     assert g2["n"] == o2["n"] and np.array_equal(g2["assign"], o2["assign"]), f"{tag}: local-map search"
@@ -603,3 +604,139 @@ def test_two_batches_in_flight_from_two_threads(ctx):
     for tb in tbs:
         tb.close()
     assert not errors, errors
+
+
+PLACEMENT_TH = 15.0
+
+
+def _placement_batch():
+    """Four two-camera KB8 frames (bases 10 .. 13) with their inputs and the oracle's results (cached): frame 0 whole, frame 1
+    cut down, frame 2 without last-frame points and without map points, frame 3 with points of which none is valid"""
+    if "placement" not in _cache:
+        sf, _ = ob.scale_factors(1.2, 8)
+        frames, lasts, Tcws, ptss, poses, oracle = [], [], [], [], [], []
+        for f in range(4):
+            fr = _kb8_base(1500, 10 + f)
+            oF, gF, kL, dL = _kb8_views(fr, sf, (700, 650) if f == 1 else None)
+            last, Tcw, pts, Rcw, tcw = _kb8_inputs(kL, dL, sf, 8000 + f, 300 + 100 * f)
+            if f == 2:
+                last = {k: v[:0] for k, v in last.items()}
+                pts = {k: v[:0] for k, v in pts.items()}
+            if f == 3:
+                last["valid"][:] = 0
+            o1 = ob.search_last_frame(oF, last, Tcw, PLACEMENT_TH, False, False, True)
+            ofr = ob.is_in_frustum(oF, ob.make_pose(Rcw, tcw, TLR), pts, 0.5, LOG_SF)
+            o2 = ob.search_local_points(oF, sc.local_points_from_frustum(ofr, pts), PLACEMENT_TH)
+            frames.append(gF); lasts.append(last); Tcws.append(Tcw); ptss.append(pts); poses.append(orb.make_pose(Rcw, tcw, TLR))
+            oracle.append((o1, ofr, o2, oF))
+        for f in (0, 1):   # the searches of the two ordinary frames find something to place
+            assert oracle[f][0]["n"] > 50 and oracle[f][2]["n"] > 50, f
+        _cache["placement"] = (frames, lasts, Tcws, ptss, poses, oracle)
+    return _cache["placement"]
+
+
+def _prepare_local_placed(tb, poses, ptss, points_ctx, frustum, ctx):
+    """prepare_local with the point arrays in points_ctx's memory and the frustum arrays absent / pageable / pinned"""
+    if frustum == "absent":
+        return tb.prepare_local(poses, ptss, want_frustum=False, ctx=points_ctx)
+    pl = tb.prepare_local(poses, ptss, ctx=points_ctx)
+    fr_ctx = ctx if frustum == "pinned" else None
+    if fr_ctx is not points_ctx:   # the frustum arrays of a second set, which stays referenced by the first
+        other = tb.prepare_local(poses, ptss, ctx=fr_ctx)
+        pl["R"], pl["outs"], pl["frustum_of"] = other["R"], other["outs"], other
+    return pl
+
+
+@pytest.mark.parametrize("cache", [3, 1])
+@pytest.mark.parametrize("frustum", ["absent", "pageable", "pinned"])
+@pytest.mark.parametrize("pin_assign", [False, True])
+@pytest.mark.parametrize("pin_points", [False, True])
+def test_every_placement_of_inputs_and_outputs_gives_the_oracles_results(ctx, pin_points, pin_assign, frustum, cache):
+    """The submits take one of two roads per kind of array: point arrays read in place (all pinned) or staged, assignments
+    written by the device into the caller's arrays (all pinned) or into the batch's result buffer, frustum fields scattered by
+    the device (all pinned), copied by the host, or not asked for - under the one-launch resolution (search_cache 3) and under
+    the claim passes (1).  Every combination gives the oracle's results on every frame, through submit + wait and through the
+    blocking calls.  holder_obs lives on the device and a search consumes it: the frames go up again in front of the second form.
+    (A pinned=True batch takes fresh pinned assignment arrays from the module's context at every upload, released with the
+    context: ~100 KB per case here.)"""
+    frames, lasts, Tcws, ptss, poses, oracle = _placement_batch()
+    pc = ctx if pin_points else None
+    with ctx.options(search_cache=cache):
+        tb = orb.TrackedBatch(ctx, max_frames=4, max_keypoints=max(F.c.N for F in frames) + 8, max_points=2048, pinned=pin_assign)
+        try:
+            pl_last = tb.prepare_last(lasts, Tcws, ctx=pc)
+            pl_local = _prepare_local_placed(tb, poses, ptss, pc, frustum, ctx)
+            kw = dict(viewing_cos_limit=0.5, log_scale_factor=LOG_SF, th=PLACEMENT_TH)
+            for form in ("submit + wait", "blocking"):
+                tb.upload(frames)
+                if form == "blocking":
+                    g1 = tb.search_last_frame(pl_last, th=PLACEMENT_TH)
+                    g2 = tb.track_local_map(pl_local, **kw)
+                else:
+                    assert tb.search_last_frame(pl_last, th=PLACEMENT_TH, submit=True) is None
+                    g1 = tb.wait()
+                    assert tb.track_local_map(pl_local, submit=True, **kw) is None
+                    g2 = tb.wait()
+                for f in range(4):
+                    _check_frame(f"{form} frame {f}", g1[f], g2[f], tb.holder_obs(f), *oracle[f], frustum=frustum != "absent")
+        finally:
+            tb.close()
+
+
+def test_one_pageable_array_among_pinned_ones_stages_the_whole_call(ctx):
+    """ONE pageable array (descriptors of frame 1 of the last-frame call, normal of frame 1 of the local-map call) among pinned
+    ones: the whole call is staged.  Same results as the oracle; and the staged road checks the octaves on the host, so a bad
+    last-frame point is reported by the SUBMIT (in place the wait reports it: test_octave_out_of_range...).  Who reports the
+    octave is the one deterministic sign of the road a call took (the stage stat is a time, the gather launch is in no stat):
+    a probe that always stages fails the in-place test, one that never stages fails this one."""
+    frames, lasts, Tcws, ptss, poses, oracle = _placement_batch()
+    tb = orb.TrackedBatch(ctx, max_frames=4, max_keypoints=max(F.c.N for F in frames) + 8, max_points=2048, pinned=True)
+    try:
+        pl_last, page_last = tb.prepare_last(lasts, Tcws, ctx=ctx), tb.prepare_last(lasts, Tcws)
+        pl_last["arr"][1].descriptors = page_last["arr"][1].descriptors
+        pl_local, page_local = tb.prepare_local(poses, ptss, ctx=ctx), tb.prepare_local(poses, ptss)
+        pl_local["P"][1].normal = page_local["P"][1].normal
+        tb.upload(frames)
+        tb.search_last_frame(pl_last, th=PLACEMENT_TH, submit=True)
+        g1 = tb.wait()
+        tb.track_local_map(pl_local, viewing_cos_limit=0.5, log_scale_factor=LOG_SF, th=PLACEMENT_TH, submit=True)
+        g2 = tb.wait()
+        for f in range(4):
+            _check_frame(f"frame {f}", g1[f], g2[f], tb.holder_obs(f), *oracle[f])
+        bad = [{k: v.copy() for k, v in last.items()} for last in lasts]
+        bad[0]["valid"][5] = 1
+        bad[0]["octave"][5] = 8
+        pl_bad, page_bad = tb.prepare_last(bad, Tcws, ctx=ctx), tb.prepare_last(bad, Tcws)
+        pl_bad["arr"][1].descriptors = page_bad["arr"][1].descriptors
+        tb.upload(frames)
+        with pytest.raises(orb.FastTrackError, match="octave out of range"):
+            tb.search_last_frame(pl_bad, th=PLACEMENT_TH, submit=True)
+        assert tb.wait() is None   # (nothing was submitted)
+    finally:
+        tb.close()
+
+
+def test_a_batch_with_nothing_to_search(ctx):
+    """no frame has a last-frame point or a map point (the call's whole work is the empty replay and one delivery): all
+    assignments -1, no match, nothing to match - with the arrays pageable and pinned; an ordinary search through the same object
+    afterwards gives the oracle's results"""
+    frames, lasts, Tcws, ptss, poses, oracle = _placement_batch()
+    none_last = [{k: v[:0] for k, v in last.items()} for last in lasts]
+    none_pts = [{k: v[:0] for k, v in pts.items()} for pts in ptss]
+    for pinned in (False, True):
+        pc = ctx if pinned else None
+        tb = orb.TrackedBatch(ctx, max_frames=4, max_keypoints=max(F.c.N for F in frames) + 8, max_points=2048, pinned=pinned)
+        try:
+            tb.upload(frames)
+            g1 = tb.search_last_frame(tb.prepare_last(none_last, Tcws, ctx=pc), th=PLACEMENT_TH)
+            g2 = tb.track_local_map(tb.prepare_local(poses, none_pts, ctx=pc), viewing_cos_limit=0.5, log_scale_factor=LOG_SF, th=PLACEMENT_TH)
+            for f in range(4):
+                for g in (g1[f], g2[f]):
+                    assert g["n"] == 0 and len(g["assign"]) == frames[f].c.N and np.all(g["assign"] == -1), (pinned, f)
+                assert g2[f]["n_to_match"] == 0, (pinned, f)
+            g1 = tb.search_last_frame(tb.prepare_last(lasts, Tcws, ctx=pc), th=PLACEMENT_TH)
+            g2 = tb.track_local_map(tb.prepare_local(poses, ptss, ctx=pc), viewing_cos_limit=0.5, log_scale_factor=LOG_SF, th=PLACEMENT_TH)
+            for f in range(4):
+                _check_frame(f"pinned {pinned} frame {f}", g1[f], g2[f], tb.holder_obs(f), *oracle[f])
+        finally:
+            tb.close()
