@@ -52,6 +52,12 @@ class LastPoints(C.Structure):
                 ("observations", C.c_void_p), ("octave", C.c_void_p), ("angle", C.c_void_p)]
 
 
+class KeyFramePoints(C.Structure):
+    """ft_keyframe_points: the map points of pKF->GetMapPointMatches() for SearchByProjection(Frame, KeyFrame)"""
+    _fields_ = [("N", C.c_int), ("valid", C.c_void_p), ("world_pos", C.c_void_p), ("max_distance", C.c_void_p),
+                ("min_distance", C.c_void_p), ("descriptors", C.c_void_p), ("observations", C.c_void_p), ("angle", C.c_void_p)]
+
+
 class FisheyeRig(C.Structure):
     _fields_ = [("cam1", C.c_float * 8), ("cam2", C.c_float * 8), ("precision", C.c_float), ("Rlr", C.c_float * 9),
                 ("tlr", C.c_float * 3)]
@@ -204,6 +210,8 @@ def lib() -> C.CDLL:
     L.ft_tracked_frame_holder_obs.argtypes = [vp, vp]
     L.ft_search_for_initialization.argtypes = [vp, C.POINTER(FrameView), C.POINTER(FrameView), vp, i, f, i, vp, ip, vp]
     L.ft_tracked_frame_search_for_initialization.argtypes = [vp, vp, vp, i, f, i, vp, ip]
+    L.ft_search_keyframe_projection.argtypes = [vp, C.POINTER(FrameView), C.POINTER(KeyFramePoints), C.POINTER(SE3), f, f, i, i, vp, ip, vp, vp]
+    L.ft_tracked_frame_search_keyframe_projection.argtypes = [vp, C.POINTER(KeyFramePoints), C.POINTER(SE3), f, f, i, i, vp, ip]
     L.ft_tracked_batch_create.argtypes = [vp, i, i, i, C.POINTER(vp)]
     L.ft_tracked_batch_destroy.argtypes = [vp]
     L.ft_tracked_batch_upload.argtypes = [vp, i, C.POINTER(FrameView)]

@@ -86,7 +86,7 @@ struct FtClaims {
 #define FT_CACHE_WORDS (2 * (FT_CACHE_CAP + 1))  // per point: left and right camera
 
 // a rigid transform: row-major 3x4 (y = R x + t), or - quat != 0 - as Sophus::SE3f holds and applies it: unit quaternion
-// q = (x, y, z, w), translation in m[3], m[7], m[11] (transform_pose, kernels_search.hip)
+// q = (x, y, z, w), translation in m[3], m[7], m[11] (transform_pose, search_dev.h)
 struct FtPose {
     float m[12];
     float q[4];
@@ -282,7 +282,56 @@ int ft_launch_init_candidates(hipStream_t st, const FtInitSearch &S);
 int ft_launch_init_resolve(hipStream_t st, const FtInitSearch &S);
 #define FT_INIT_MAX_LDS (150 * 1024)
 
+// ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:2087-2208;
+// kernels_reloc.hip), the matcher of Tracking::Relocalization.  A POINT is an entry of pKF->GetMapPointMatches(), in index order.
+// A candidate is a key (distance, cell x, cell y, index) as make_key (search_dev.h) builds it: ascending keys = ascending
+// distance, then the order of Frame::GetFeaturesInArea.  Per point the FT_RELOC_TOP smallest keys (ascending) and a segment of
+// FT_RELOC_SEG keys with all of them, unordered; a point with more candidates than the segment holds raises status[0] and the
+// resolution writes nothing (FT_ERR_CAPACITY).
+#define FT_RELOC_TOP 4
+#define FT_RELOC_SEG 256
+struct FtRelocProj {
+    float u, v;
+    int level;  // PredictScale
+    int go;     // the point is searched (valid, projects into the image bounds, inside its distance range)
+};
+struct FtRelocSearch {
+    FtDevFrame F;  // the current frame with its grid
+    int N;         // points
+    const uint8_t *valid;
+    const float *worldPos, *maxDist, *minDist;
+    const uint8_t *desc;
+    const int *obs;
+    const float *angle;  // may be null unless checkOrientation
+    FtPose Tcw;          // Sophus form (quat != 0)
+    float logScaleFactor, th;
+    int orbDist, checkOrientation;
+    FtRelocProj *proj;         // [N]
+    unsigned long long *top;   // [N][FT_RELOC_TOP]
+    unsigned long long *seg;   // [N][FT_RELOC_SEG]
+    int *segCount;             // [N] candidates of a point (clamped to FT_RELOC_SEG)
+    int *status;               // [0] != 0: a point has more candidates than its segment holds
+    int *holder;               // [F.N] holder_obs of the frame, in / out (held on entry <=> != -1)
+    int *assign;               // [F.N]
+    int *bestDist, *bestIdx;   // [N]
+    int *nMatches;             // [1]
+};
+// the three launches of a call, in this order
+int ft_launch_reloc_project(hipStream_t st, const FtRelocSearch &S);
+int ft_launch_reloc_candidates(hipStream_t st, const FtRelocSearch &S);
+int ft_launch_reloc_resolve(hipStream_t st, const FtRelocSearch &S);
+// dynamic LDS of the resolution: a taken bit per left keypoint and the keypoint a point took (<= FT_INIT_MAX_LDS)
+inline size_t ft_reloc_lds_bytes(int nLeftKeys, int nPoints) { return 4 * (((size_t)nLeftKeys + 31) / 32 + (size_t)nPoints); }
+
 #ifdef __HIPCC__
+// rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero
+__device__ __forceinline__ int init_bin(float angle1, float angle2) {
+    float rot = __fsub_rn(angle1, angle2);
+    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+    int bin = (int)roundf(__fmul_rn(rot, 1.0f / FT_HISTO_LENGTH));
+    if (bin == FT_HISTO_LENGTH) bin = 0;
+    return bin;
+}
 struct Window {
     int minCX, maxCX, minCY, maxCY;
     bool empty;

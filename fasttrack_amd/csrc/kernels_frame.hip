@@ -9,7 +9,7 @@
 #include <algorithm>
 
 #include "search_dev.h"
-#include "libm_f32.h"  // (predict_scale: logf_glibc)
+#include "libm_f32.h"
 
 namespace {
 
@@ -107,23 +107,6 @@ __global__ __launch_bounds__(256) void k_build_grid_batch(const FtBatchJob *__re
 // (src/MapPoint.cc:531-546): one thread per local map point.  Float expressions are evaluated in the
 // order the oracle states (no contraction); log(ratio) binds to logf (MapPoint.cc:539), reproduced by libm_f32.h.
 // ------------------------------------------------------------------------------------------------
-// Eigen's sum of three terms (dot, squaredNorm, a coefficient of a small matrix product): redux_novec_unroller splits the
-// range in halves, e0 + (e1 + e2) (see the oracle's note at orc_is_in_frustum)
-__device__ __forceinline__ float dot3(const float *a, const float *b) {
-    return __fadd_rn(__fmul_rn(a[0], b[0]), __fadd_rn(__fmul_rn(a[1], b[1]), __fmul_rn(a[2], b[2])));
-}
-// sqrtf is correctly rounded here (-fhip-fp32-correctly-rounded-divide-sqrt); __fsqrt_rn maps to the native approximation
-__device__ __forceinline__ float norm3(const float *a) { return sqrtf(dot3(a, a)); }
-
-__device__ __forceinline__ int predict_scale(float maxDistanceRaw, float dist, float logScaleFactor, int nLevels) {
-    const float ratio = __fdiv_rn(maxDistanceRaw, dist);
-    const float lg = ft_libm::logf_glibc(ratio);
-    int nScale = (int)ceilf(__fdiv_rn(lg, logScaleFactor));
-    if (nScale < 0) nScale = 0;
-    else if (nScale >= nLevels) nScale = nLevels - 1;
-    return nScale;
-}
-
 __device__ __forceinline__ void frustum_point(const FtDevFrame &F, const FtFrustumPose &T, const FtDevMapPoints &P, float viewingCosLimit,
                                               float logScaleFactor, int farPoints, float thFar, const FtFrustumOut &O, int i) {
     if (i >= P.M) return;

@@ -184,15 +184,6 @@ __global__ __launch_bounds__(64 * FT_INIT_WPB) void k_init_candidates(FtInitSear
     if (lane == 0) S.segCount[row] = min(count, S.cap2);
 }
 
-// rotation bin of a match (src/ORBmatcher.cc:817-823): float arithmetic, round() half away from zero
-__device__ __forceinline__ int init_bin(float angle1, float angle2) {
-    float rot = __fsub_rn(angle1, angle2);
-    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-    int bin = (int)roundf(__fmul_rn(rot, 1.0f / FT_HISTO_LENGTH));
-    if (bin == FT_HISTO_LENGTH) bin = 0;
-    return bin;
-}
-
 // LDS: state[ord] = vMatchedDistance << 16 | row of vnMatches21 (0xffff / 0xffff = INT_MAX / -1), then rowMatch[row] = the ord
 // the row holds, -1 = never matched, -2 - ord = evicted from ord (what its rotation bin was computed with).
 #define FT_INIT_RES_T 1024

@@ -1,8 +1,8 @@
 // Device side of the projection searches: what more than one of kernels_search.hip, kernels_search_rows.hip,
-// kernels_resolve.hip and kernels_frame.hip uses - a frame's pointers, the candidate key, the claim records of a pass, the
+// kernels_resolve.hip, kernels_frame.hip and kernels_reloc.hip uses - a frame's pointers, the candidate key, the claim records of a pass, the
 // meta word of a candidate list, a window's entry, the camera models.  A helper that only one of those files uses lives in
 // that file.  Everything here is __device__ __forceinline__ (or a type) in an anonymous namespace: nothing links across files.
-// Device only: nothing includes this header except those four .hip files.
+// Device only: nothing includes this header except those five .hip files.
 #pragma once
 #include "kb8_math.h"
 #include "ft_search.h"
@@ -240,6 +240,156 @@ __device__ __forceinline__ void project_cam(const FtDevFrame &F, const float p[3
         uv[0] = __fadd_rn(__fmul_rn(__fmul_rn(F.cam[0], r), ft_cos_f(psi)), F.cam[2]);
         uv[1] = __fadd_rn(__fmul_rn(__fmul_rn(F.cam[1], r), ft_sin_f(psi)), F.cam[3]);
     }
+}
+
+
+// The keypoints of camera `cam` whose grid cell lies in window w and whose octave lies in the level band of the search,
+// handed to fn(entry) lane-parallel.  The frame's grid (k_build_grid) is a CSR PER OCTAVE: the keypoints of octave o in the
+// cells (cx, minCY .. maxCY) are one contiguous range of entries - a map point looks at the keypoints GetFeaturesInArea would
+// return for it (window AND level band: the band keeps 13 - 40 % of a window's keypoints, least where the windows are
+// largest), where a grid over all octaves made the first pass of a search read every keypoint of the window.  Without a grid
+// every keypoint's cell is computed and tested.
+// minLevel / maxLevel as Frame::GetFeaturesInArea takes them (src/Frame.cc:714-729): no check at all unless minLevel > 0 or
+// maxLevel >= 0; maxLevel < 0 = no upper bound.
+template <class Fn>
+__device__ __forceinline__ void for_window(const FtDevFrame &F, const FramePtrs &Q, int cam, const ft_keypoint *keys, int n, const Window &w,
+                                           int minLevel, int maxLevel, int lane, Fn fn) {
+    if (Q.gridStart[cam]) {
+        // One lane per (octave, column of cells) range, a wave scan lays the ranges end to end, and the lanes take the
+        // entries 64 at a time - two rounds per trip: record and descriptor of an entry sit at the entry's position, so a
+        // round is one memory round trip, and a wide window a chain of them.
+        const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
+        const int lo = checkLevels ? min(max(minLevel, 0), F.nlevels - 1) : 0;  // (octaves beyond the table are filed under its last bucket)
+        const int hi = (checkLevels && maxLevel >= 0) ? min(maxLevel, F.nlevels - 1) : F.nlevels - 1;
+        const int ncolsW = w.maxCX - w.minCX + 1;
+        const int npairs = (hi - lo + 1) * ncolsW;  // (<= 0: an empty band)
+        const int *gs = Q.gridStart[cam];
+        const float4 *rec = Q.gridRec[cam];
+        const uint4 *gd = (const uint4 *)Q.gridDesc[cam];
+        const unsigned colMagic = div_magic_u(ncolsW);
+        for (int p0 = 0; p0 < npairs; p0 += 64) {
+            const int np = min(64, npairs - p0);
+            int b = 0, cnt = 0, myCol = 0;
+            if (lane < np) {
+                const int pidx = p0 + lane;
+                const int oi = colMagic ? (int)__umulhi((unsigned)pidx, colMagic) : pidx;
+                myCol = w.minCX + (pidx - oi * ncolsW);
+                const int *col = gs + (size_t)(lo + oi) * (FT_GRID_CELLS + 1) + myCol * FT_GRID_ROWS;
+                b = col[w.minCY];
+                cnt = col[w.maxCY + 1] - b;
+            }
+            int incl = cnt;  // inclusive scan over the lanes
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(incl, d);
+                if (lane >= d) incl += y;
+            }
+            const int total = __builtin_amdgcn_readlane(incl, 63);
+            auto locate = [&](int t, int &pos, int &cx) {
+                int r = 0;  // the range entry t falls into: the number of ranges that end at or before t
+                for (int c = 0; c < np - 1; c++) r += t >= __builtin_amdgcn_readlane(incl, c) ? 1 : 0;
+                const int cb = __shfl(b, r), cEnd = __shfl(incl, r), cCnt = __shfl(cnt, r);
+                cx = __shfl(myCol, r);
+                pos = cb + (t - (cEnd - cCnt));
+            };
+            auto hand = [&](const float4 &r, const uint4 &d0, const uint4 &d1, int cx) {
+                WinEntry e;
+                e.x = r.x; e.y = r.y; e.uright = r.z;
+                const int io = __float_as_int(r.w);
+                e.idx = io & 0xffffff;
+                e.octave = io >> 24;  // (signed: the keypoint's own octave, whatever bucket it was filed under)
+                e.cx = cx;
+                e.cy = (int)roundf(__fmul_rn(__fsub_rn(r.y, F.mnMinY), F.invH));  // Frame::PosInGrid, as k_build_grid filed it
+                e.d[0] = (unsigned long long)d0.x | ((unsigned long long)d0.y << 32);
+                e.d[1] = (unsigned long long)d0.z | ((unsigned long long)d0.w << 32);
+                e.d[2] = (unsigned long long)d1.x | ((unsigned long long)d1.y << 32);
+                e.d[3] = (unsigned long long)d1.z | ((unsigned long long)d1.w << 32);
+                fn(e);
+            };
+            for (int t0 = 0; t0 < total; t0 += 128) {
+                const int tA = t0 + lane, tB = t0 + 64 + lane;
+                int posA, cxA, posB = 0, cxB = 0;
+                locate(min(tA, total - 1), posA, cxA);
+                const bool second = t0 + 64 < total;  // wave-uniform
+                if (second) locate(min(tB, total - 1), posB, cxB);
+                const float4 rA = rec[posA];
+                const uint4 a0 = gd[2 * (size_t)posA], a1 = gd[2 * (size_t)posA + 1];
+                float4 rB = rA;
+                uint4 b0 = a0, b1 = a1;
+                if (second) {
+                    rB = rec[posB];
+                    b0 = gd[2 * (size_t)posB];
+                    b1 = gd[2 * (size_t)posB + 1];
+                }
+                if (tA < total) hand(rA, a0, a1, cxA);
+                if (second && tB < total) hand(rB, b0, b1, cxB);
+            }
+        }
+        return;
+    }
+    const uint8_t *desc = Q.desc + (cam == 0 ? 0 : (size_t)F.Nleft * 32);
+    for (int idx = lane; idx < n; idx += 64) {
+        const ft_keypoint kp = keys[idx];
+        const int cx = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.mnMinX), F.invW));
+        const int cy = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.mnMinY), F.invH));
+        if (cx < 0 || cx >= FT_GRID_COLS || cy < 0 || cy >= FT_GRID_ROWS) continue;  // never entered the grid
+        if (cx < w.minCX || cx > w.maxCX || cy < w.minCY || cy > w.maxCY) continue;
+        WinEntry e;
+        e.x = kp.x; e.y = kp.y;
+        e.uright = (cam == 0 && F.Nleft == -1 && Q.uright) ? Q.uright[idx] : -1.0f;
+        e.idx = idx; e.octave = kp.octave; e.cx = cx; e.cy = cy;
+        const unsigned long long *dp = (const unsigned long long *)(desc + (size_t)idx * 32);
+        e.d[0] = dp[0]; e.d[1] = dp[1]; e.d[2] = dp[2]; e.d[3] = dp[3];
+        fn(e);
+    }
+}
+
+// ---- poses and distances (the float chains of the reference, every operation rounded on its own) ----
+__device__ __forceinline__ void transform34(const float *T, const float x[3], float y[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+        y[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4 * r], x[0]), __fmul_rn(T[4 * r + 1], x[1])),
+                                   __fmul_rn(T[4 * r + 2], x[2])),
+                         T[4 * r + 3]);
+}
+
+// Sophus::SE3f * point as the reference's CPU branch evaluates `Tcw * x3Dw` (src/ORBmatcher.cc:1805) and `GetRelativePoseTrl() *
+// x3Dc` (:1900): Thirdparty/Sophus/sophus/so3.hpp:358-367 - uv = q.vec().cross(p); uv += uv; p + q.w() * uv + q.vec().cross(uv) -
+// then + translation (se3.hpp:321-324); every product and sum rounded on its own, coefficient order as Eigen's cross()
+__device__ __forceinline__ void cross3_rn(const float a[3], const float b[3], float c[3]) {
+    c[0] = __fsub_rn(__fmul_rn(a[1], b[2]), __fmul_rn(a[2], b[1]));
+    c[1] = __fsub_rn(__fmul_rn(a[2], b[0]), __fmul_rn(a[0], b[2]));
+    c[2] = __fsub_rn(__fmul_rn(a[0], b[1]), __fmul_rn(a[1], b[0]));
+}
+__device__ __forceinline__ void transform_pose(const float *m, const float *q, int quat, const float x[3], float y[3]) {
+    if (!quat) {
+        transform34(m, x, y);
+        return;
+    }
+    float uv[3], c[3];
+    cross3_rn(q, x, uv);
+#pragma unroll
+    for (int i = 0; i < 3; i++) uv[i] = __fadd_rn(uv[i], uv[i]);
+    cross3_rn(q, uv, c);
+#pragma unroll
+    for (int i = 0; i < 3; i++) y[i] = __fadd_rn(__fadd_rn(__fadd_rn(x[i], __fmul_rn(q[3], uv[i])), c[i]), m[4 * i + 3]);
+}
+
+// Eigen's sum of three terms (dot, squaredNorm, a coefficient of a small matrix product): redux_novec_unroller splits the
+// range in halves, e0 + (e1 + e2) (see the oracle's note at orc_is_in_frustum)
+__device__ __forceinline__ float dot3(const float *a, const float *b) {
+    return __fadd_rn(__fmul_rn(a[0], b[0]), __fadd_rn(__fmul_rn(a[1], b[1]), __fmul_rn(a[2], b[2])));
+}
+// sqrtf is correctly rounded here (-fhip-fp32-correctly-rounded-divide-sqrt); __fsqrt_rn maps to the native approximation
+__device__ __forceinline__ float norm3(const float *a) { return sqrtf(dot3(a, a)); }
+
+__device__ __forceinline__ int predict_scale(float maxDistanceRaw, float dist, float logScaleFactor, int nLevels) {
+    const float ratio = __fdiv_rn(maxDistanceRaw, dist);
+    const float lg = ft_libm::logf_glibc(ratio);
+    int nScale = (int)ceilf(__fdiv_rn(lg, logScaleFactor));
+    if (nScale < 0) nScale = 0;
+    else if (nScale >= nLevels) nScale = nLevels - 1;
+    return nScale;
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // Host side of the projection searches, shared by the translation units of the entry-point families (search_view.cpp,
-// tracked_frame.cpp, init_search.cpp, tracked_batch.cpp): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
+// tracked_frame.cpp, init_search.cpp, reloc_search.cpp, tracked_batch.cpp): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
 // (reference include/Kernels/KernelController.h:40-46) together with the acceptance loops the reference keeps in the caller
 // (src/ORBmatcher.cc:241-308, 2013-2081).  Windowing, level/box tests and every Hamming distance run on the device
 // (kernels_search*.hip, kernels_resolve.hip, kernels_frame.hip); the host only marshals arrays, drives the fixed-point passes and
@@ -628,7 +628,8 @@ struct ft_tracked_frame {
     std::vector<int> holder;
     int passesLast = 0, passesLocal = 0;  // claim passes of the previous search of each kind: the next one's burst size (fixedPoint)
     // ORBmatcher::SearchForInitialization with this frame as the current one (runInitSearch): keypoints of octave 0, and the
-    // call's arena with its pinned mirror (grow-only; the candidate segments are level0 x level0 words of two frames)
+    // call's arena with its pinned mirror (grow-only; the candidate segments are level0 x level0 words of two frames).  The
+    // relocalisation search (reloc_search.cpp) takes its arena from the same pair: both hold nothing between calls.
     int level0 = 0;
     uint8_t *d_init = nullptr, *h_init = nullptr;
     size_t initDevBytes = 0, initPinBytes = 0;

@@ -458,6 +458,22 @@ class KernelController:
         return dict(matches12=m12[:N1], prev_matched=prev, n=n.value, matched_distance=dist[:N2])
 
     @staticmethod
+    def search_keyframe_projection(ctx: Context, Cur: FrameView, kf: dict, Tcw: "SE3", log_scale_factor, th, orb_dist,
+                                   check_orientation=True):
+        """ORBmatcher(0.9, check_orientation).SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
+        (ORBmatcher.cc:2087-2208; ft_search_keyframe_projection).  kf: dict(valid, world_pos, max_distance, min_distance,
+        descriptors, observations, angle) over pKF->GetMapPointMatches(), valid = pMP && !isBad() && !sAlreadyFound.count(pMP).
+        Updates Cur.holder_obs -> dict(assign, n, best_dist, best_idx)."""
+        keep = {}
+        K, M = _keyframe_points(kf, keep)
+        assign = np.full(max(Cur.N, 1), -1, np.int32)
+        bd, bi = np.zeros(max(M, 1), np.int32), np.zeros(max(M, 1), np.int32)
+        n = C.c_int()
+        check(lib().ft_search_keyframe_projection(ctx._h, C.byref(Cur.c), C.byref(K), C.byref(Tcw.c), float(log_scale_factor), float(th),
+                                                  int(orb_dist), int(check_orientation), ptr(assign), C.byref(n), ptr(bd), ptr(bi)))
+        return dict(assign=assign[:Cur.N], n=n.value, best_dist=bd[:M], best_idx=bi[:M])
+
+    @staticmethod
     def descriptor_distance(ctx: Context, a, b):
         a, b = np.ascontiguousarray(a, np.uint8), np.ascontiguousarray(b, np.uint8)
         n = len(a)
@@ -649,6 +665,20 @@ def is_in_frustum(ctx: Context, F: "FrameView", pose, pts: dict, viewing_cos_lim
     return r
 
 
+def _keyframe_points(kf: dict, keep: dict):
+    """-> (ft_keyframe_points, N) over the arrays of kf, which `keep` keeps alive; kf["angle"] may be missing / None"""
+    M = len(kf["valid"])
+    K = _capi.KeyFramePoints()
+    K.N = M
+    for k, dt in (("valid", np.uint8), ("world_pos", np.float32), ("max_distance", np.float32), ("min_distance", np.float32),
+                  ("descriptors", np.uint8), ("observations", np.int32), ("angle", np.float32)):
+        if kf.get(k) is None:
+            continue
+        keep[k] = np.ascontiguousarray(kf[k], dt)
+        setattr(K, k, ptr(keep[k]))
+    return K, M
+
+
 class TrackedFrame:
     """Device-resident frame for the projection searches (ft_tracked_frame_*)."""
 
@@ -713,6 +743,18 @@ class TrackedFrame:
         check(lib().ft_tracked_frame_search_for_initialization(self._h, initial._h, ptr(prev) if N1 else None, int(window),
                                                                float(nn_ratio), int(check_orientation), ptr(m12), C.byref(n)))
         return dict(matches12=m12[:N1], prev_matched=prev, n=n.value)
+
+    def search_keyframe_projection(self, kf: dict, Tcw: "SE3", log_scale_factor, th, orb_dist, check_orientation=True):
+        """SearchByProjection(self, pKF, sAlreadyFound, th, ORBdist) on the resident frame
+        (ft_tracked_frame_search_keyframe_projection; kf as KernelController.search_keyframe_projection takes it); the resident
+        holder_obs carries the writes -> dict(assign, n)."""
+        keep = {}
+        K, _ = _keyframe_points(kf, keep)
+        assign = np.full(max(self.N, 1), -1, np.int32)
+        n = C.c_int()
+        check(lib().ft_tracked_frame_search_keyframe_projection(self._h, C.byref(K), C.byref(Tcw.c), float(log_scale_factor), float(th),
+                                                                int(orb_dist), int(check_orientation), ptr(assign), C.byref(n)))
+        return dict(assign=assign[:self.N], n=n.value)
 
     def track_local_map(self, pose, pts: dict, viewing_cos_limit, log_scale_factor, th, nn_ratio=0.8, far_points=False,
                         th_far_points=0.0):

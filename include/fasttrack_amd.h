@@ -414,6 +414,43 @@ FT_API int ft_search_for_initialization(ft_context *ctx, const ft_frame_view *F1
                                         int *matched_distance);
 
 /* ------------------------------------------------------------------------------------------------
+ * ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*> &sAlreadyFound, th, ORBdist)
+ * (src/ORBmatcher.cc:2087-2208), the matcher Tracking::Relocalization calls behind PnP (src/Tracking.cc:3924: th 10, ORBdist 100;
+ * :3938: th 3, ORBdist 64; ORBmatcher matcher2(0.9, true)).  For the keyframe's map points IN INDEX ORDER: x3Dc = Tcw * x3Dw in
+ * the Sophus form (see ft_search_last_frame_se3), mpCamera->project, the image bounds - NO depth test: a point behind the camera
+ * whose projection lands inside the bounds is searched (:2112-2119) -, dist3D = |x3Dw - Ow| with Ow = Tcw.inverse().translation()
+ * (the conjugate of q applied to -t; q is taken as the unit quaternion it is, without the renormalisation of SO3's
+ * constructor) against [0.8f min_distance, 1.2f max_distance], PredictScale, radius = th * mvScaleFactors[level], the candidates
+ * GetFeaturesInArea(u, v, radius, level - 1, level + 1) of the LEFT camera in that function's order (mvuRight is never looked at).
+ * A candidate whose mvpMapPoints entry is not NULL is skipped WHATEVER its Observations(): on entry "held" is holder_obs != -1, and
+ * a keypoint written by an earlier point of the call is held for every later one.  Best distance with strict <; bestDist <= ORBdist
+ * writes the keypoint; rotation histogram of angle[i] - mvKeysUn[bestIdx2].angle, ComputeThreeMaxima, removal (:2186-2205).
+ * Precondition: x3Dc.z != 0 for every valid point (the reference's behaviour is undefined there: NaN into an int cast).
+ * assign[i2] (size Cur->N) = the keyframe index whose point ends up in mvpMapPoints[i2], else -1; entries >= Nleft of a
+ * two-camera frame are -1.  holder_obs of a keypoint that keeps its write becomes observations[i]; one the histogram removed is
+ * -1 again.  best_dist / best_idx (size K->N, may be NULL): bestDist / bestIdx2 as the loop leaves them for point i, 256 / -1 for a
+ * point that was skipped or found every candidate held.  *n_matches: the return value.  Everything equals the reference's CPU branch
+ * bit for bit (there is no GPU boundary for this function in the reference).
+ * Launches per call: 4 (the frame's grid, then three kernels: projection, the candidates of every point, the sequential
+ * resolution with histogram and outputs) - a fixed sequence, one wait; kernel timing names them kernel.reloc_*.
+ * FT_ERR_CAPACITY, with NO output written and holder_obs unchanged, when the window of one point holds more than 256 free
+ * keypoints of its level band, or when 4 bytes per point plus a bit per keypoint exceed 150 KB.  0 <= orb_dist <= 255.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ft_keyframe_points {
+    int N;                      /* pKF->GetMapPointMatches().size() */
+    const uint8_t *valid;       /* pMP && !pMP->isBad() && !sAlreadyFound.count(pMP) */
+    const float *world_pos;     /* N x 3, GetWorldPos() */
+    const float *max_distance;  /* mfMaxDistance (the 1.2f / 0.8f of the invariance getters are applied inside, as in ft_map_points) */
+    const float *min_distance;  /* mfMinDistance */
+    const uint8_t *descriptors; /* N x 32, GetDescriptor() */
+    const int *observations;    /* Observations(): what holder_obs of a written keypoint becomes */
+    const float *angle;         /* pKF->mvKeysUn[i].angle; may be NULL when check_orientation == 0 */
+} ft_keyframe_points;
+FT_API int ft_search_keyframe_projection(ft_context *ctx, ft_frame_view *Cur, const ft_keyframe_points *K, const ft_se3 *Tcw,
+                                         float log_scale_factor, float th, int orb_dist, int check_orientation, int *assign,
+                                         int *n_matches, int *best_dist, int *best_idx);
+
+/* ------------------------------------------------------------------------------------------------
  * Frustum test + scale prediction for the local map points: Frame::isInFrustum /
  * isInFrustumChecks (src/Frame.cc:536-610, 1308-1382) with MapPoint::PredictScale (src/MapPoint.cc:531-546),
  * the host loop in front of SearchByProjection (src/Tracking.cc:3503-3522).
@@ -497,6 +534,14 @@ FT_API int ft_tracked_frame_track_local_map(ft_tracked_frame *tf, const ft_frame
 FT_API int ft_tracked_frame_search_for_initialization(ft_tracked_frame *current, ft_tracked_frame *initial, float *prev_matched,
                                                       int window_size, float nn_ratio, int check_orientation, int *matches12,
                                                       int *n_matches);
+/* ft_search_keyframe_projection on the resident frame: only K and the pose are marshalled; the frame, its grid and holder_obs
+ * stay where ft_tracked_frame_upload / bind_stereo left them, and the resident holder_obs is updated in place, so that a second
+ * call (src/Tracking.cc:3938) or ft_tracked_frame_track_local_map sees the writes.  Launches per call: 3 (4 for a frame loaded
+ * under option search_grid = 0: its grid is built for the call); statistic "tracked.search_keyframe_projection.launches" sums
+ * them.  No point, no valid point or no keypoint returns without a launch. */
+FT_API int ft_tracked_frame_search_keyframe_projection(ft_tracked_frame *tf, const ft_keyframe_points *K, const ft_se3 *Tcw,
+                                                       float log_scale_factor, float th, int orb_dist, int check_orientation,
+                                                       int *assign, int *n_matches);
 /* current holder_obs (size N of the resident frame) */
 FT_API int ft_tracked_frame_holder_obs(ft_tracked_frame *tf, int *holder_obs);
 

@@ -240,6 +240,19 @@ struct KernelController {
         assign.resize(CurrentFrame.N);
         return nm;
     }
+    // ORBmatcher(0.9, mbCheckOrientation).SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) on a frame view
+    // (ORBmatcher.cc:2087-2208; the reference has no GPU boundary for it): pKF.valid carries sAlreadyFound, Tcw =
+    // se3Of(CurrentFrame.GetPose()); h_bestDist / h_bestIdx2 (pKF.N ints, may be null): what the loop leaves per point
+    static int SearchByProjection(Context &ctx, ft_frame_view &CurrentFrame, const ft_keyframe_points &pKF, const ft_se3 &Tcw,
+                                  float mfLogScaleFactor, float th, int ORBdist, bool mbCheckOrientation, std::vector<int> &assign,
+                                  int *h_bestDist = nullptr, int *h_bestIdx2 = nullptr) {
+        assign.assign(CurrentFrame.N > 0 ? CurrentFrame.N : 1, -1);
+        int nm = 0;
+        check(ft_search_keyframe_projection(ctx.handle(), &CurrentFrame, &pKF, &Tcw, mfLogScaleFactor, th, ORBdist,
+                                            mbCheckOrientation ? 1 : 0, assign.data(), &nm, h_bestDist, h_bestIdx2));
+        assign.resize(CurrentFrame.N);
+        return nm;
+    }
 };
 
 // ft_se3 of a Sophus::SE3f (or anything with unit_quaternion().coeffs() = x y z w and translation()): the pose form of the
@@ -321,6 +334,19 @@ public:
         int nm = 0;
         check(ft_tracked_frame_search_last_frame_se3(h_, &LastFrame, &Tcw, Trl, th, bForward, bBackward, mbCheckOrientation,
                                                      assign.data(), &nm));
+        assign.resize(N_);
+        return nm;
+    }
+    // ORBmatcher(0.9, mbCheckOrientation).SearchByProjection(CurrentFrame = *this, pKF, sAlreadyFound, th, ORBdist), the matcher of
+    // Tracking::Relocalization                                                   ORBmatcher.cc:2087, Tracking.cc:3924, :3938
+    // pKF: the keyframe's GetMapPointMatches() as arrays; sAlreadyFound is folded into pKF.valid (pMP && !pMP->isBad() &&
+    // !sAlreadyFound.count(pMP)).  assign[i2] = the keyframe index whose point ends up in mvpMapPoints[i2], else -1.
+    int SearchByProjection(const ft_keyframe_points &pKF, const ft_se3 &Tcw, float mfLogScaleFactor, float th, int ORBdist,
+                           bool mbCheckOrientation, std::vector<int> &assign) {
+        assign.assign(N_ > 0 ? N_ : 1, -1);
+        int nm = 0;
+        check(ft_tracked_frame_search_keyframe_projection(h_, &pKF, &Tcw, mfLogScaleFactor, th, ORBdist, mbCheckOrientation ? 1 : 0,
+                                                          assign.data(), &nm));
         assign.resize(N_);
         return nm;
     }
