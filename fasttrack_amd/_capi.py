@@ -74,6 +74,19 @@ class BowSide(C.Structure):
                 ("fv_features", C.c_void_p), ("descriptors", C.c_void_p), ("angles", C.c_void_p)]
 
 
+class TriangKeyFrame(C.Structure):
+    """ft_triang_keyframe: what ORBmatcher::SearchForTriangulation reads of a KeyFrame"""
+    _fields_ = [("n", C.c_int), ("n_left", C.c_int), ("keys", C.c_void_p), ("descriptors", C.c_void_p), ("n_nodes", C.c_int),
+                ("fv_nodes", C.c_void_p), ("fv_offsets", C.c_void_p), ("fv_features", C.c_void_p), ("has_point", C.c_void_p),
+                ("uright", C.c_void_p), ("two_cameras", C.c_int), ("cam_model", C.c_int), ("cam", C.c_float * 8), ("cam2", C.c_float * 8),
+                ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("nlevels", C.c_int)]
+
+
+class TriangPair(C.Structure):
+    """ft_triang_pair: the constants of one (pKF1, pKF2) pair"""
+    _fields_ = [("ep", C.c_float * 2), ("F12", C.c_float * 9), ("R12", C.c_float * 36), ("t12", C.c_float * 12), ("kb8_precision", C.c_float)]
+
+
 class FramePose(C.Structure):
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("tlr", C.c_float * 3)]
 
@@ -237,6 +250,7 @@ def lib() -> C.CDLL:
     L.ft_vocabulary_info.argtypes = [vp, ip, ip, ip, ip]
     L.ft_bow_transform.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, i, ip, vp, vp, vp, i, ip]
     L.ft_search_by_bow.argtypes = [vp, C.POINTER(BowSide), vp, C.POINTER(BowSide), i, f, i, vp, ip]
+    L.ft_search_for_triangulation.argtypes = [vp, C.POINTER(TriangKeyFrame), i, C.POINTER(TriangKeyFrame), C.POINTER(TriangPair), i, i, i, vp, vp, vp]
     L.ft_selftest_libm.argtypes = [vp, i, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_ulonglong),
                                    C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]
     L.ft_octree_distribute.argtypes = [vp, i, i, i, i, i, i, vp, i, ip]

@@ -323,6 +323,37 @@ int ft_launch_reloc_resolve(hipStream_t st, const FtRelocSearch &S);
 // dynamic LDS of the resolution: a taken bit per left keypoint and the keypoint a point took (<= FT_INIT_MAX_LDS)
 inline size_t ft_reloc_lds_bytes(int nLeftKeys, int nPoints) { return 4 * (((size_t)nLeftKeys + 31) / 32 + (size_t)nPoints); }
 
+// ORBmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (src/ORBmatcher.cc:1006-1245;
+// kernels_triang.hip) for keyframe 1 against every neighbour of a call.  Everything lives in ONE arena (what the host stages and
+// copies up in one piece, then the outputs); a record holds byte offsets into it, so a kernel forms its addresses from the
+// arena pointer it got as an argument.
+#define FT_TRIANG_NONE 0xffffffffu  // FtTriangSide::uright: the keyframe has no mvuRight (all -1)
+struct FtTriangSide {
+    int n, nLeft, nNodes;           // features, KeyFrame::NLeft, FeatureVector entries
+    unsigned keys, desc;            // ft_keypoint[n], n x 32
+    unsigned nodes, offsets, feats; // the FeatureVector in CSR form
+    unsigned hasPoint, uright;      // uint8[n], float[n] (or FT_TRIANG_NONE)
+    unsigned sf, sigma2;            // mvScaleFactors, mvLevelSigma2
+    float cam[2][8];                // mpCamera, mpCamera2
+};
+struct FtTriangJob {  // one neighbour
+    FtTriangSide K2;
+    float ep[2], F12[9], R12[4][9], t12[4][3], precision;  // ft_triang_pair
+    unsigned matches, bestDist;                            // int[K1.n] each
+};
+struct FtTriangCall {
+    uint8_t *arena;
+    FtTriangSide K1;
+    unsigned k1;        // K1 once more, in the arena: what a lane selects by its own feature (the camera) is read from memory
+    unsigned nodeOf;    // int[K1.n]: the FeatureVector entry that lists feature i, -1 = none (a stopped word)
+    unsigned jobs;      // FtTriangJob[nNeighbours]
+    unsigned nMatches;  // int[nNeighbours]
+    int nNeighbours, camModel, twoCameras, onlyStereo, coarse, checkOrientation;
+};
+// the two launches of a call, in this order
+int ft_launch_triang_match(hipStream_t st, const FtTriangCall &T);
+int ft_launch_triang_finish(hipStream_t st, const FtTriangCall &T);
+
 #ifdef __HIPCC__
 // rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero
 __device__ __forceinline__ int init_bin(float angle1, float angle2) {
@@ -331,6 +362,29 @@ __device__ __forceinline__ int init_bin(float angle1, float angle2) {
     int bin = (int)roundf(__fmul_rn(rot, 1.0f / FT_HISTO_LENGTH));
     if (bin == FT_HISTO_LENGTH) bin = 0;
     return bin;
+}
+// ComputeThreeMaxima (src/ORBmatcher.cc:2210-2251) on the bin sizes: bit b of the result = bin b is kept
+__device__ __forceinline__ int three_maxima_keep(const int *hist) {
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int b = 0; b < FT_HISTO_LENGTH; b++) {
+        const int sz = hist[b];
+        if (sz > max1) {
+            max3 = max2; max2 = max1; max1 = sz;
+            ind3 = ind2; ind2 = ind1; ind1 = b;
+        } else if (sz > max2) {
+            max3 = max2; max2 = sz;
+            ind3 = ind2; ind2 = b;
+        } else if (sz > max3) {
+            max3 = sz; ind3 = b;
+        }
+    }
+    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
+    int keep = 0;
+    if (ind1 >= 0) keep |= 1 << ind1;
+    if (ind2 >= 0) keep |= 1 << ind2;
+    if (ind3 >= 0) keep |= 1 << ind3;
+    return keep;
 }
 struct Window {
     int minCX, maxCX, minCY, maxCY;

@@ -13,15 +13,6 @@
 
 namespace {
 
-// minimum over the 16 lanes of a DPP row, returned in every lane of the row
-__device__ __forceinline__ unsigned row_min_u32(unsigned v) {
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true));  // row_half_mirror
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true));  // row_mirror
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_bow_walk(FtBowTree t, const uint8_t *desc, int n, int nidLevel,
                                                   unsigned *wordOut, unsigned *nodeOut, double *weightOut) {
     const int lane = threadIdx.x & 63, sub = lane & 15;

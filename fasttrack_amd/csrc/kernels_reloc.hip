@@ -66,30 +66,6 @@ __global__ __launch_bounds__(256) void k_reloc_project(FtRelocSearch S) {
     S.proj[i] = pj;
 }
 
-// ComputeThreeMaxima (src/ORBmatcher.cc:2210-2251) on the bin sizes: bit b of the result = bin b is kept
-__device__ __forceinline__ int three_maxima_keep(const int *hist) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int b = 0; b < FT_HISTO_LENGTH; b++) {
-        const int sz = hist[b];
-        if (sz > max1) {
-            max3 = max2; max2 = max1; max1 = sz;
-            ind3 = ind2; ind2 = ind1; ind1 = b;
-        } else if (sz > max2) {
-            max3 = max2; max2 = sz;
-            ind3 = ind2; ind2 = b;
-        } else if (sz > max3) {
-            max3 = sz; ind3 = b;
-        }
-    }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-    int keep = 0;
-    if (ind1 >= 0) keep |= 1 << ind1;
-    if (ind2 >= 0) keep |= 1 << ind2;
-    if (ind3 >= 0) keep |= 1 << ind3;
-    return keep;
-}
-
 // key joins the ascending t[0 .. FT_RELOC_TOP)
 __device__ __forceinline__ void reloc_top_insert(unsigned long long t[FT_RELOC_TOP], unsigned long long key) {
 #pragma unroll

@@ -77,6 +77,15 @@ __device__ __forceinline__ unsigned long long row_min_u64(unsigned long long v) 
     return v;
 }
 
+// the same for 32-bit keys
+__device__ __forceinline__ unsigned row_min_u32(unsigned v) {
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true));  // row_half_mirror
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true));  // row_mirror
+    return v;
+}
+
 // maximum over the row of 16 lanes, in every lane of it
 __device__ __forceinline__ int row_max_i32(int v) {
     v = max(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));

@@ -1037,6 +1037,79 @@ def search_by_bow(ctx: Context, kf: BowSide, kf_has_point, frame: BowSide, frame
     return dict(matches=m[:frame.c.n], n=n.value)
 
 
+class TriangKeyFrame:
+    """What ORBmatcher::SearchForTriangulation reads of a KeyFrame (ft_triang_keyframe).  keys: KP_DTYPE records (mvKeysUn, or
+    mvKeys followed by mvKeysRight when n_left != -1); fv_*: mFeatVec as Vocabulary.transform returns it; has_point[i] =
+    GetMapPoint(i) != NULL; uright: mvuRight or None (all -1); cam / cam2: fx fy cx cy k1..k4.  Owns the arrays."""
+
+    def __init__(self, keys, descriptors, fv_nodes, fv_offsets, fv_features, has_point, scale_factors, level_sigma2, cam, cam2=None,
+                 cam_model=0, two_cameras=False, n_left=-1, uright=None):
+        self.keys = np.ascontiguousarray(keys, _capi.KP_DTYPE)
+        self.descriptors = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        self.fv_nodes = np.ascontiguousarray(fv_nodes, np.uint32)
+        self.fv_offsets = np.ascontiguousarray(fv_offsets, np.int32)
+        self.fv_features = np.ascontiguousarray(fv_features, np.uint32)
+        if len(self.fv_offsets) == 0:
+            self.fv_offsets = np.zeros(1, np.int32)
+        self.has_point = np.ascontiguousarray(has_point, np.uint8)
+        self.uright = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        self.scale_factors = np.ascontiguousarray(scale_factors, np.float32)
+        self.level_sigma2 = np.ascontiguousarray(level_sigma2, np.float32)
+        n = len(self.keys)
+        assert len(self.descriptors) == n == len(self.has_point) and (self.uright is None or len(self.uright) == n)
+        assert len(self.scale_factors) == len(self.level_sigma2) and len(self.fv_offsets) == len(self.fv_nodes) + 1
+        c = _capi.TriangKeyFrame()
+        c.n, c.n_left, c.n_nodes = n, int(n_left), len(self.fv_nodes)
+        c.keys, c.descriptors, c.has_point = ptr(self.keys), ptr(self.descriptors), ptr(self.has_point)
+        c.fv_nodes, c.fv_offsets, c.fv_features = ptr(self.fv_nodes), ptr(self.fv_offsets), ptr(self.fv_features)
+        c.uright = None if self.uright is None else ptr(self.uright)
+        c.two_cameras, c.cam_model = int(bool(two_cameras)), int(cam_model)
+        c.cam[:] = [float(v) for v in (list(cam) + [0.0] * 8)[:8]]
+        c.cam2[:] = [float(v) for v in (list(cam if cam2 is None else cam2) + [0.0] * 8)[:8]]
+        c.scale_factors, c.level_sigma2, c.nlevels = ptr(self.scale_factors), ptr(self.level_sigma2), len(self.scale_factors)
+        self.c = c
+
+
+def make_triang_pair(ep=(0, 0), F12=None, R12=None, t12=None, kb8_precision=1e-6):
+    """ft_triang_pair: ep; F12 (3 x 3, pinhole); R12 / t12: one pose (T12) or four (ll, lr, rl, rr) for two-camera keyframes"""
+    P = _capi.TriangPair()
+    P.ep[:] = [float(v) for v in np.asarray(ep, np.float32).reshape(2)]
+    P.F12[:] = [float(v) for v in (np.zeros(9, np.float32) if F12 is None else np.asarray(F12, np.float32).reshape(9))]
+    R = np.zeros((4, 9), np.float32)
+    t = np.zeros((4, 3), np.float32)
+    if R12 is not None:
+        Rs = np.asarray(R12, np.float32).reshape(-1, 9)
+        ts = np.asarray(t12, np.float32).reshape(-1, 3)
+        assert len(Rs) == len(ts) and len(Rs) in (1, 4)
+        R[:len(Rs)], t[:len(ts)] = Rs, ts
+    P.R12[:] = [float(v) for v in R.reshape(-1)]
+    P.t12[:] = [float(v) for v in t.reshape(-1)]
+    P.kb8_precision = float(kb8_precision)
+    return P
+
+
+def search_for_triangulation(ctx: Context, kf1: TriangKeyFrame, neighbours, pairs, only_stereo=False, coarse=False,
+                             check_orientation=True):
+    """ORBmatcher(0.6, check_orientation).SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) for pKF1 against
+    every neighbour in one call (ft_search_for_triangulation).  neighbours: TriangKeyFrame list, pairs: make_triang_pair list ->
+    dict(matches12 [k, kf1.n], n [k], best_dist [k, kf1.n], pairs = per neighbour the (idx1, idx2) rows of vMatchedPairs)"""
+    nn, n1 = len(neighbours), kf1.c.n
+    assert len(pairs) == nn
+    K2 = (_capi.TriangKeyFrame * max(nn, 1))(*[k.c for k in neighbours])
+    P = (_capi.TriangPair * max(nn, 1))(*pairs)
+    cnt = np.zeros(max(nn, 1), np.int32)
+    mflat, bflat = np.full(max(nn * n1, 1), -1, np.int32), np.full(max(nn * n1, 1), 50, np.int32)
+    check(lib().ft_search_for_triangulation(ctx._h, C.byref(kf1.c), nn, K2, P, int(bool(only_stereo)), int(bool(coarse)),
+                                            int(bool(check_orientation)), ptr(mflat), ptr(cnt), ptr(bflat)))
+    m = mflat[:nn * n1].reshape(nn, n1)
+    bd = bflat[:nn * n1].reshape(nn, n1)
+    out = []
+    for k in range(nn):
+        i = np.nonzero(m[k] >= 0)[0]
+        out.append(np.stack([i, m[k][i]], axis=1).astype(np.int64))
+    return dict(matches12=m, n=cnt[:nn], best_dist=bd, pairs=out)
+
+
 def features_in_area(ctx: Context, F: "FrameView", x, y, r, min_level, max_level, right=None, capacity=512):
     """Frame::GetFeaturesInArea for arrays of queries (ft_features_in_area) -> list of index arrays"""
     x = np.ascontiguousarray(x, np.float32); y = np.ascontiguousarray(y, np.float32); r = np.ascontiguousarray(r, np.float32)

@@ -709,6 +709,68 @@ typedef struct ft_bow_side {
 FT_API int ft_search_by_bow(ft_context *ctx, const ft_bow_side *kf, const uint8_t *kf_has_point, const ft_bow_side *frame,
                             int frame_nleft, float nn_ratio, int check_orientation, int *matches, int *n_matches);
 
+/* ----------------------------------------------------------------------------------------------
+ * ORBmatcher::SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, vMatchedPairs, bOnlyStereo, bCoarse)
+ * (src/ORBmatcher.cc:1006-1245), the matcher of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:388-466), for keyframe 1
+ * against ALL the neighbours that passed the caller's baseline filter in one call: the calls of the reference's neighbour loop
+ * share keyframe 1 and are independent of each other.
+ * For every vocabulary node the two FeatureVectors share and every feature idx1 of keyframe 1 in it: skipped when it has a map
+ * point (has_point: the pointer alone, not isBad(), :1073) or when only_stereo && !bStereo1 (bStereo1 = !two_cameras &&
+ * uright[idx1] >= 0, :1078).  A candidate idx2 of the same node in keyframe 2 is eligible when it has no map point, is stereo if
+ * only_stereo, DescriptorDistance <= TH_LOW (50), is not near the epipole (only when neither feature is stereo and the keyframes
+ * have one camera: rejected when distex^2 + distey^2 < 100 * scale_factors2[kp2.octave], strictly, :1125-1133) and, unless
+ * coarse, passes pCamera1->epipolarConstrain (:1171).  The match is the eligible candidate of smallest distance, among equals the
+ * LAST of the node's list (the scan skips on dist > bestDist, :1116; vbMatched2 is never written, :1048, so no feature sees what
+ * another one chose).  Then the rotation histogram of kp1.angle - kp2.angle, ComputeThreeMaxima and the removal (:1186-1232).
+ * Keypoints: mvKeysUn when n_left == -1, else mvKeys followed by mvKeysRight (bRight = idx >= n_left).
+ * The constraint, float without contraction: pinhole (src/CameraModels/Pinhole.cpp:107-129) a = (x1 F(0,0) + y1 F(1,0)) + F(2,0),
+ * b, c likewise, num = (a x2 + b y2) + c, den = a a + b b, false when den == 0, else (double)(num num / den) < 3.84 *
+ * (double)level_sigma2_2[kp2.octave]; KannalaBrandt8 (src/CameraModels/KannalaBrandt8.cpp:216-220) TriangulateMatches(...) >
+ * 0.0001f as in ft_fisheye_stereo, for two-camera keyframes with the cameras and the pose of the pairing ll, lr, rl, rr of the
+ * two features (:1135-1169).  The constants of a pair are Sophus / Eigen expressions on the poses (:1013-1042) and stay with the
+ * caller (ft_triang_pair; INTEGRATION.md has the lines).
+ * matches12[k * kf1->n + idx1] = vMatches12[idx1] against neighbour k (vMatchedPairs = the entries >= 0 in ascending idx1),
+ * n_matches[k] = the return value, best_dist (same shape, may be NULL) = bestDist as the loop leaves it: 50 where nothing was
+ * eligible or the feature was skipped.  Everything equals the reference's CPU text bit for bit (the null vector of
+ * TriangulateMatches as documented at ft_fisheye_stereo).  n_neighbours == 1 is the reference's single call; a neighbour with
+ * n == 0 or without a shared node gives all -1 and 0.
+ * Launches per call: 2 whatever n_neighbours (the candidates of every feature against every neighbour; histogram, removal and
+ * counts, a workgroup per neighbour), one copy up, one copy down, one wait; kernel timing names them kernel.triang_match /
+ * kernel.triang_finish.  kf1->n == 0 or n_neighbours == 0 returns without a launch.
+ * FT_ERR_INVALID: a pinhole keyframe with two_cameras; keyframes of one call that differ in two_cameras or in cam_model (the
+ * reference reads an uninitialised R12 there); an fv_features entry >= n or listed twice; a keypoint octave outside
+ * [0, nlevels); fv_nodes not strictly ascending.  n < 2^20 per keyframe; FT_ERR_CAPACITY when one call's keyframes exceed 4 GB.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ft_triang_keyframe {
+    int n;                       /* KeyFrame::N */
+    int n_left;                  /* KeyFrame::NLeft (-1: one camera) */
+    const ft_keypoint *keys;     /* [n] mvKeysUn, or mvKeys then mvKeysRight: pt, octave, angle are read */
+    const uint8_t *descriptors;  /* n x 32, mDescriptors */
+    int n_nodes;                 /* mFeatVec in the CSR form of ft_bow_transform / ft_bow_side */
+    const unsigned *fv_nodes;    /* [n_nodes] ascending */
+    const int *fv_offsets;       /* [n_nodes + 1] */
+    const unsigned *fv_features; /* [fv_offsets[n_nodes]] */
+    const uint8_t *has_point;    /* [n] GetMapPoint(i) != NULL */
+    const float *uright;         /* [n] mvuRight, or NULL: all -1 */
+    int two_cameras;             /* mpCamera2 != NULL */
+    int cam_model;               /* 0 pinhole, 1 KannalaBrandt8 */
+    float cam[8], cam2[8];       /* fx fy cx cy k1 k2 k3 k4 of mpCamera / mpCamera2 (KannalaBrandt8 only) */
+    const float *scale_factors;  /* [nlevels] mvScaleFactors */
+    const float *level_sigma2;   /* [nlevels] mvLevelSigma2 */
+    int nlevels;
+} ft_triang_keyframe;
+typedef struct ft_triang_pair {
+    float ep[2];         /* pKF2->mpCamera->project(T2w * pKF1->GetCameraCenter()) (:1016-1019) */
+    float F12[9];        /* pinhole: K1.transpose().inverse() * hat(t12) * R12 * K2.inverse(), row-major */
+    float R12[4][9];     /* KannalaBrandt8: rotationMatrix() (row-major) of T12 (one camera) or Tll; then of Tlr, Trl, Trr */
+    float t12[4][3];     /* translation() of the same */
+    float kb8_precision; /* KannalaBrandt8::precision */
+} ft_triang_pair;
+FT_API int ft_search_for_triangulation(ft_context *ctx, const ft_triang_keyframe *kf1, int n_neighbours,
+                                       const ft_triang_keyframe *kf2 /* [n_neighbours] */, const ft_triang_pair *pairs /* [n_neighbours] */,
+                                       int only_stereo, int coarse, int check_orientation, int *matches12 /* n_neighbours x kf1->n */,
+                                       int *n_matches /* [n_neighbours] */, int *best_dist /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -570,4 +570,28 @@ inline int SearchByBoW(Context &ctx, const ORBVocabulary::FeatureVector &kfFeatV
     return nm;
 }
 
+// ORBmatcher(0.6, mbCheckOrientation).SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse)
+// (src/ORBmatcher.cc:1006-1245) for pKF1 against every neighbour of LocalMapping::CreateNewMapPoints in one call
+// (ft_search_for_triangulation): vpKF2 are the neighbours that passed the caller's baseline filter, vPairs the constants of each
+// pair (ep, F12 or R12 / t12).  vMatchedPairs[k] is the reference's vMatchedPairs against vpKF2[k], the return
+// value its nmatches per neighbour.
+inline std::vector<int> SearchForTriangulation(Context &ctx, const ft_triang_keyframe &pKF1, const std::vector<ft_triang_keyframe> &vpKF2,
+                                               const std::vector<ft_triang_pair> &vPairs, bool bOnlyStereo, bool bCoarse,
+                                               bool mbCheckOrientation,
+                                               std::vector<std::vector<std::pair<size_t, size_t>>> &vMatchedPairs) {
+    const size_t nn = vpKF2.size(), n1 = pKF1.n > 0 ? (size_t)pKF1.n : 0;
+    if (vPairs.size() != nn) throw std::invalid_argument("SearchForTriangulation: one ft_triang_pair per neighbour");
+    std::vector<int> vMatches12(nn * n1 + 1, -1), nmatches(nn + 1, 0);
+    check(ft_search_for_triangulation(ctx.handle(), &pKF1, (int)nn, vpKF2.data(), vPairs.data(), bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0,
+                                      mbCheckOrientation ? 1 : 0, vMatches12.data(), nmatches.data(), nullptr));
+    vMatchedPairs.assign(nn, {});
+    for (size_t k = 0; k < nn; k++) {
+        vMatchedPairs[k].reserve(nmatches[k] > 0 ? (size_t)nmatches[k] : 0);
+        for (size_t i = 0; i < n1; i++)
+            if (vMatches12[k * n1 + i] >= 0) vMatchedPairs[k].push_back(std::make_pair(i, (size_t)vMatches12[k * n1 + i]));
+    }
+    nmatches.resize(nn);
+    return nmatches;
+}
+
 }  // namespace fasttrack

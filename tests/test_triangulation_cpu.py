@@ -1,0 +1,132 @@
+"""ORBmatcher::SearchForTriangulation on the CPU: the sequential restatement (tests/triangulation_ref.py) against an independent
+order-free formulation, hand-built cases with expectations written out from the reference text, the four pairings of two-camera
+keyframes, non-vacuity of the committed scenarios, and the new entry point's declaration."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import binding as ob
+from tests import triangulation_cases as tc
+from tests import triangulation_ref as tr
+from tests.init_search_ref import HISTO_LENGTH, TH_LOW, distances, rotation_bin, three_maxima
+
+f32 = np.float32
+
+
+def order_free(kf1, kf2, pair, only_stereo, coarse, check_orientation):
+    """All pairs of a shared node, filtered by tests that do not depend on each other, then the minimum of (dist, -position)."""
+    N1 = len(kf1["keys"])
+    m12, best = np.full(N1, -1, np.int32), np.full(N1, TH_LOW, np.int32)
+    shared = sorted(set(kf1["fv_nodes"].tolist()) & set(kf2["fv_nodes"].tolist()))
+    ep = np.asarray(pair["ep"], f32)
+    R, t = np.asarray(pair["R12"], f32).reshape(-1, 3, 3), np.asarray(pair["t12"], f32).reshape(-1, 3)
+    two = kf1["two_cameras"]
+
+    def stereo(kf, i):
+        return (not kf["two_cameras"]) and kf["uright"] is not None and kf["uright"][i] >= 0
+
+    for node in shared:
+        j1, j2 = int(np.nonzero(kf1["fv_nodes"] == node)[0][0]), int(np.nonzero(kf2["fv_nodes"] == node)[0][0])
+        l1 = kf1["fv_features"][kf1["fv_offsets"][j1]:kf1["fv_offsets"][j1 + 1]].tolist()
+        l2 = kf2["fv_features"][kf2["fv_offsets"][j2]:kf2["fv_offsets"][j2 + 1]].tolist()
+        for i1 in l1:
+            if kf1["has_point"][i1] or (only_stereo and not stereo(kf1, i1)):
+                continue
+            keys = []
+            for pos, i2 in enumerate(l2):
+                if kf2["has_point"][i2] or (only_stereo and not stereo(kf2, i2)):
+                    continue
+                dist = int(distances(kf1["descriptors"][i1], kf2["descriptors"][[i2]])[0])
+                if dist > TH_LOW:
+                    continue
+                kp1, kp2 = kf1["keys"][i1], kf2["keys"][i2]
+                if not stereo(kf1, i1) and not stereo(kf2, i2) and not two:
+                    ex, ey = f32(ep[0] - kp2["x"]), f32(ep[1] - kp2["y"])
+                    if f32(f32(ex * ex) + f32(ey * ey)) < f32(f32(100) * kf2["scale_factors"][kp2["octave"]]):
+                        continue
+                if not coarse:
+                    s1, s2 = kf1["level_sigma2"][kp1["octave"]], kf2["level_sigma2"][kp2["octave"]]
+                    if kf1["cam_model"] == 0:
+                        ok = tr.pinhole_constrain(pair["F12"], kp1, kp2, s2)
+                    else:
+                        r1 = two and i1 >= kf1["n_left"]
+                        r2 = two and i2 >= kf2["n_left"]
+                        k = (2 * int(r1) + int(r2)) if two else 0
+                        ok = tr.kb8_constrain(kf1["cam2"] if r1 else kf1["cam"], kf2["cam2"] if r2 else kf2["cam"], R[k], t[k],
+                                              pair["kb8_precision"], kp1, kp2, s1, s2)
+                    if not ok:
+                        continue
+                keys.append((dist, -pos, i2))
+            if keys:
+                d, _, i2 = min(keys)
+                m12[i1], best[i1] = i2, d
+    if check_orientation:
+        bins = {i: rotation_bin(kf1["keys"][i]["angle"], kf2["keys"][m12[i]]["angle"]) for i in range(N1) if m12[i] >= 0}
+        keep = three_maxima([sum(1 for b in bins.values() if b == h) for h in range(HISTO_LENGTH)])
+        for i, b in bins.items():
+            if b not in keep:
+                m12[i] = -1
+    return dict(matches12=m12, n=int((m12 >= 0).sum()), best_dist=best)
+
+
+FLAGS = [(False, False, True), (False, True, True), (True, False, True), (False, False, False)]
+
+
+@pytest.mark.parametrize("form,seed,forward", tc.MAIN)
+def test_sequential_and_order_free_forms_agree(form, seed, forward):
+    S = tc.scenario(form, seed, forward=forward)
+    for flags in FLAGS if form == "pinhole" else FLAGS[:2]:
+        for kf2, pair in zip(S["neighbours"], S["pairs"]):
+            a = tr.search_for_triangulation(S["kf1"], kf2, pair, *flags)
+            b = order_free(S["kf1"], kf2, pair, *flags)
+            assert np.array_equal(a["matches12"], b["matches12"]) and a["n"] == b["n"] and np.array_equal(a["best_dist"], b["best_dist"])
+            assert a["pairs"] == [(i, int(m)) for i, m in enumerate(a["matches12"]) if m >= 0]
+
+
+@pytest.mark.parametrize("case", tc.hand_built(), ids=lambda c: c["name"])
+def test_hand_built_cases(case):
+    for fn in (tr.search_for_triangulation, order_free):
+        r = fn(case["kf1"], case["kf2"], case["pair"], *case["flags"])
+        assert np.array_equal(r["matches12"], case["matches12"]), (fn.__name__, r["matches12"])
+        assert r["n"] == case["n"] and np.array_equal(r["best_dist"], case["best_dist"]), (fn.__name__, r["n"], r["best_dist"])
+
+
+def test_the_four_pairings_reach_the_oracle_with_their_own_cameras_and_pose():
+    kf1, kf2, P = tc.four_pairings()
+    calls = []
+    tr.search_for_triangulation(kf1, kf2, P, False, False, False, calls=calls)
+    assert len(calls) == 4   # (l, l), (l, r), (r, l), (r, r): equal distances, so every candidate reaches the constraint
+    want = [(tc.KB8_CAM, tc.KB8_CAM, 0), (tc.KB8_CAM, tc.KB8_CAM2, 1), (tc.KB8_CAM2, tc.KB8_CAM, 2), (tc.KB8_CAM2, tc.KB8_CAM2, 3)]
+    for (ca, cb, R, t), (wa, wb, k) in zip(calls, want):
+        assert ca == tuple(f32(v) for v in wa) and cb == tuple(f32(v) for v in wb)
+        assert np.array_equal(R, P["R12"][k]) and np.array_equal(t, P["t12"][k])
+    assert len({c[2].tobytes() for c in calls}) == 4
+
+
+def test_committed_scenarios_are_not_vacuous():
+    tot = dict(nearest_rejected=0, next_won=0, epipole_rejections=0, ties=0, removed_by_histogram=0)
+    for form, seed, forward in tc.MAIN:
+        S = tc.scenario(form, seed, forward=forward)
+        for kf2, pair in zip(S["neighbours"], S["pairs"]):
+            r = tr.search_for_triangulation(S["kf1"], kf2, pair)
+            assert r["n"] >= 100, (form, seed, r["n"])
+            for k in tot:
+                tot[k] += r["stats"][k]
+    assert all(v >= 1 for v in tot.values()), tot
+
+
+def test_descriptor_distance_is_the_oracles():
+    rng = np.random.default_rng(1)
+    d = rng.integers(0, 256, (20, 32), dtype=np.uint8)
+    assert [int(v) for v in distances(d[0], d)] == [ob.descriptor_distance(d[0], d[i]) for i in range(20)]
+
+
+def test_new_symbol_is_declared_and_exported():
+    from fasttrack_amd import _capi
+    assert "ft_search_for_triangulation" in _capi.declared_symbols()
+    L = C.CDLL(_capi.LIB_PATH)
+    assert hasattr(L, "ft_search_for_triangulation")
+    assert C.sizeof(_capi.TriangPair) == 4 * (2 + 9 + 36 + 12 + 1)
+    from fasttrack_amd import orb
+    assert callable(orb.search_for_triangulation) and callable(orb.make_triang_pair)
