@@ -87,6 +87,19 @@ class TriangPair(C.Structure):
     _fields_ = [("ep", C.c_float * 2), ("F12", C.c_float * 9), ("R12", C.c_float * 36), ("t12", C.c_float * 12), ("kb8_precision", C.c_float)]
 
 
+class FusePoints(C.Structure):
+    """ft_fuse_points: the map points of a Fuse call"""
+    _fields_ = [("M", C.c_int), ("world_pos", C.c_void_p), ("normal", C.c_void_p), ("max_distance", C.c_void_p),
+                ("min_distance", C.c_void_p), ("descriptors", C.c_void_p)]
+
+
+class FuseTarget(C.Structure):
+    """ft_fuse_target: one (keyframe, camera) of a Fuse call"""
+    _fields_ = [("kf", C.POINTER(FrameView)), ("right", C.c_int), ("cam2", C.c_float * 8), ("Tcw", SE3), ("Ow", C.c_float * 3),
+                ("log_scale_factor", C.c_float), ("inv_level_sigma2", C.c_void_p), ("valid", C.c_void_p), ("th", C.c_float),
+                ("check_reprojection", C.c_int)]
+
+
 class FramePose(C.Structure):
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("tlr", C.c_float * 3)]
 
@@ -251,6 +264,7 @@ def lib() -> C.CDLL:
     L.ft_bow_transform.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, i, ip, vp, vp, vp, i, ip]
     L.ft_search_by_bow.argtypes = [vp, C.POINTER(BowSide), vp, C.POINTER(BowSide), i, f, i, vp, ip]
     L.ft_search_for_triangulation.argtypes = [vp, C.POINTER(TriangKeyFrame), i, C.POINTER(TriangKeyFrame), C.POINTER(TriangPair), i, i, i, vp, vp, vp]
+    L.ft_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseTarget), vp, vp, vp, vp]
     L.ft_selftest_libm.argtypes = [vp, i, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_ulonglong),
                                    C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]
     L.ft_octree_distribute.argtypes = [vp, i, i, i, i, i, i, vp, i, ip]

@@ -354,6 +354,42 @@ struct FtTriangCall {
 int ft_launch_triang_match(hipStream_t st, const FtTriangCall &T);
 int ft_launch_triang_finish(hipStream_t st, const FtTriangCall &T);
 
+// ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1247-1437,
+// :1439-1554; kernels_fuse.hip) for one list of map points against every target of a call.  A TARGET is one (keyframe, camera):
+// the host hands the searched camera's keypoints over as a one-camera device frame (F.Nleft == -1; the right camera of a
+// two-camera keyframe with its own keys, descriptor rows and mpCamera2 in F.cam), so that the grid and the window scan are those of
+// any frame; idxOffset (NLeft for bRight) turns a keypoint of that frame back into the keyframe's index.  Every pointer of a
+// record points into the call's device arena (the kernels re-derive them from it: FramePtrs, search_dev.h).
+struct FtFuseTarget {
+    FtDevFrame F;          // with its grid: gridStart[0] / gridRec[0] / gridDesc[0], filled by k_fuse_grid
+    FtPose Tcw;            // Sophus form (quat != 0)
+    float Ow[3];
+    float logScaleFactor, th;
+    float invSigma2[FT_MAX_LEVELS];  // mvInvLevelSigma2, read when checkReproj
+    int checkReproj;       // the chi-square test of the SE3 overload (:1371-1395)
+    int idxOffset;
+    const uint8_t *valid;  // [M] or null: all
+    int *bestIdx, *bestDist;  // [M] each
+    uint8_t *stage;        // [M] or null
+    int *nFound;           // [1], zero on entry
+};
+struct FtFusePoints {
+    int M;
+    const float *worldPos, *normal, *maxDist, *minDist;
+    const uint8_t *desc;
+};
+// exit codes of a point (include/fasttrack_amd.h, ft_fuse_search)
+#define FT_FUSE_SEARCHED 0
+#define FT_FUSE_SKIPPED 1
+#define FT_FUSE_DEPTH 2
+#define FT_FUSE_IMAGE 3
+#define FT_FUSE_DISTANCE 4
+#define FT_FUSE_NORMAL 5
+#define FT_FUSE_EMPTY 6
+// the two launches of a call, in this order; arena: the call's device arena, targets: its FtFuseTarget[nTargets]
+int ft_launch_fuse_grid(hipStream_t st, void *arena, const FtFuseTarget *targets, int nTargets, int maxLevels);
+int ft_launch_fuse_search(hipStream_t st, void *arena, const FtFuseTarget *targets, int nTargets, const FtFusePoints &P);
+
 #ifdef __HIPCC__
 // rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero
 __device__ __forceinline__ int init_bin(float angle1, float angle2) {

@@ -13,81 +13,7 @@
 
 namespace {
 
-// Frame::AssignFeaturesToGrid (src/Frame.cc:409-440) as one CSR per octave: workgroup (octave o, camera) counting-sorts the
-// camera's keypoints of octave o by cell cx * 48 + cy in LDS and files them behind the keypoints of the lower octaves (their
-// number is counted on the way).  An octave outside [0, nlevels) is filed under the nearest bucket; the searches test the
-// keypoint's own octave anyway.  The order inside a cell is free (the searches order candidates by (distance, cx, cy, index)
-// keys).  start: [nlevels][FT_GRID_CELLS + 1] absolute entry positions; rec / desc: the entries (ft_search.h).
-__device__ __forceinline__ void build_grid_body(const FtDevFrame &F, const FramePtrs &Q, int oct, int cam, int *startL, int *startR,
-                                                float4 *recL, uint8_t *descL, float4 *recR, uint8_t *descR) {
-    __shared__ int cnt[FT_GRID_CELLS + 1];
-    __shared__ int wsum[4], wbelow[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = cam == 0 ? (F.Nleft == -1 ? F.N : F.Nleft) : (F.Nleft == -1 ? 0 : F.N - F.Nleft);
-    const ft_keypoint *keys = cam == 0 ? Q.keys : Q.keysR;
-    int *start = (cam == 0 ? startL : startR);
-    if (!start) return;
-    start += (size_t)oct * (FT_GRID_CELLS + 1);
-    for (int c = tid; c <= FT_GRID_CELLS; c += 256) cnt[c] = 0;
-    __syncthreads();
-    auto cellOf = [&](const ft_keypoint &kp) -> int {
-        const int cx = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.mnMinX), F.invW));
-        const int cy = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.mnMinY), F.invH));
-        if (cx < 0 || cx >= FT_GRID_COLS || cy < 0 || cy >= FT_GRID_ROWS) return -1;
-        return cx * FT_GRID_ROWS + cy;
-    };
-    int below = 0;  // keypoints of the grid in lower buckets
-    for (int i = tid; i < n; i += 256) {
-        const ft_keypoint kp = keys[i];
-        const int c = cellOf(kp);
-        if (c < 0) continue;
-        const int bkt = min(max(kp.octave, 0), F.nlevels - 1);
-        if (bkt < oct) below++;
-        else if (bkt == oct) atomicAdd(&cnt[c], 1);
-    }
-    below = wave_sum_i32(below);
-    if (lane == 0) wbelow[wave] = below;
-    __syncthreads();
-    // exclusive scan of the 3072 counts: 12 consecutive cells per thread
-    constexpr int PER = FT_GRID_CELLS / 256;
-    int local = 0;
-    for (int k = 0; k < PER; k++) local += cnt[tid * PER + k];
-    int incl = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    const int base = wbelow[0] + wbelow[1] + wbelow[2] + wbelow[3];
-    int run = base + incl - local;
-    for (int w = 0; w < wave; w++) run += wsum[w];
-    const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    for (int k = 0; k < PER; k++) {
-        const int c = tid * PER + k, v = cnt[c];
-        start[c] = run;
-        cnt[c] = run;  // becomes the fill cursor of the cell
-        run += v;
-    }
-    if (tid == 0) start[FT_GRID_CELLS] = base + total;
-    __syncthreads();
-    float4 *rec = cam == 0 ? recL : recR;
-    uint8_t *gdesc = cam == 0 ? descL : descR;
-    const uint8_t *desc = Q.desc + (cam == 0 ? 0 : (size_t)F.Nleft * 32);
-    for (int i = tid; i < n; i += 256) {
-        const ft_keypoint kp = keys[i];
-        const int c = cellOf(kp);
-        if (c < 0 || min(max(kp.octave, 0), F.nlevels - 1) != oct) continue;
-        const int p = atomicAdd(&cnt[c], 1);
-        const float ur = (cam == 0 && F.Nleft == -1 && Q.uright) ? Q.uright[i] : -1.0f;
-        rec[p] = make_float4(kp.x, kp.y, ur, __int_as_float((i & 0xffffff) | (kp.octave << 24)));
-        const uint4 *d = (const uint4 *)(desc + (size_t)i * 32);
-        uint4 *o = (uint4 *)(gdesc + (size_t)p * 32);
-        o[0] = d[0];
-        o[1] = d[1];
-    }
-}
+// (build_grid_body, the counting sort of one (octave, camera) of a frame: search_dev.h - kernels_fuse.hip files the views of a call with it)
 __global__ __launch_bounds__(256) void k_build_grid(FtDevFrame F, int *startL, int *startR, float4 *recL, uint8_t *descL, float4 *recR,
                                                     uint8_t *descR) {
     build_grid_body(F, frame_ptrs(F, FT_NO_REBASE), blockIdx.x, blockIdx.y, startL, startR, recL, descL, recR, descR);

@@ -21,7 +21,6 @@ namespace {
 // What is computed per entry - box, level band, uright test, Hamming distance, key - and what is filed are exactly the
 // general kernel's (the order of a list is free), so the later passes cannot tell which kernel ran the first one.  First pass:
 // nothing is locked but what was held before the call.
-__device__ __forceinline__ int row_shfl(int v, int srcLane) { return __shfl(v, srcLane); }
 // the two smallest keys of a row, in every lane of it
 __device__ __forceinline__ void row_two_min(unsigned long long &k0, unsigned long long &k1) {
     const unsigned long long m0 = row_min_u64(k0);
@@ -30,98 +29,7 @@ __device__ __forceinline__ void row_two_min(unsigned long long &k0, unsigned lon
     k0 = m0;
 }
 
-// The window scan of a row's point, in three steps through a small LDS list of the row (FT_ROW_LIST entries; the lanes of a row
-// belong to one wave, whose LDS operations are served in order - no barrier):
-//   expand  a lane per (octave, column of cells) range, a DPP scan lays the ranges end to end, and every range lane writes the
-//           grid positions of its entries (with the column in the top byte) at their places in the list - where the first form of
-//           this loop looked the range of every entry up again, 16 entries at a time, by a chain of np - 1 shuffles;
-//   filter  16 entries at a time: the 16-byte record, level band and box test of GetFeaturesInArea (in_box), the survivors packed
-//           to the front of the list by a ballot of the row - the cell ranges of a window hold ~2.4 x the keypoints of the box, and
-//           the other 58 % leave here without their descriptor having been loaded;
-//   visit   fn(entry, real) for the survivors, 16 at a time: descriptor, cell row, and whatever the search does with them.
-// Windows with more entries than the list holds go through it in parts.  What fn sees is what it saw before minus the entries
-// in_box rejects (the order inside a list is free).
-#define FT_ROW_LIST 64
-__device__ __forceinline__ void row_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-template <class Fn>
-__device__ __forceinline__ void row_for_window(const FtDevFrame &F, const FramePtrs &Q, int cam, const Window &w, int minLevel, int maxLevel,
-                                               float bx, float by, float br, int sub, int rowBase, unsigned *list, Fn fn) {
-    const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
-    const int lo = checkLevels ? min(max(minLevel, 0), F.nlevels - 1) : 0;
-    const int hi = (checkLevels && maxLevel >= 0) ? min(maxLevel, F.nlevels - 1) : F.nlevels - 1;
-    const int ncolsW = w.maxCX - w.minCX + 1;
-    const int npairs = (hi - lo + 1) * ncolsW;  // (<= 0: an empty band)
-    const int *gs = Q.gridStart[cam];
-    const float4 *rec = Q.gridRec[cam];
-    const uint4 *gd = (const uint4 *)Q.gridDesc[cam];
-    const unsigned colMagic = div_magic_u(ncolsW);
-    for (int p0 = 0; p0 < npairs; p0 += 16) {  // (row-uniform)
-        const int np = min(16, npairs - p0);
-        int b = 0, cnt = 0, myCol = 0;
-        if (sub < np) {
-            const int pidx = p0 + sub;
-            const int oi = colMagic ? (int)__umulhi((unsigned)pidx, colMagic) : pidx;
-            myCol = w.minCX + (pidx - oi * ncolsW);
-            const int *col = gs + (size_t)(lo + oi) * (FT_GRID_CELLS + 1) + myCol * FT_GRID_ROWS;
-            b = col[w.minCY];
-            cnt = col[w.maxCY + 1] - b;
-        }
-        int incl = cnt;  // inclusive scan over the 16 lanes of the row (lanes shifted in from outside the row read 0)
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, true);  // row_shr:1
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, true);  // row_shr:2
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, true);  // row_shr:4
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, true);  // row_shr:8
-        const int total = row_shfl(incl, rowBase + 15);
-        const int start = incl - cnt;
-        const unsigned tag = (unsigned)b | ((unsigned)myCol << 24);  // (grid positions stay below 2^24, columns below 64)
-        for (int w0 = 0; w0 < total; w0 += FT_ROW_LIST) {  // (row-uniform)
-            const int nw = min(FT_ROW_LIST, total - w0);
-            // expand: the part of this lane's range that falls into [w0, w0 + nw)
-            for (int k = max(0, w0 - start), k1 = min(cnt, w0 + nw - start); k < k1; k++) list[start + k - w0] = tag + (unsigned)k;
-            row_lds_sync();
-            // filter: survivors of the box to the front (an entry is read before its group writes, and a group writes below its
-            // own first entry + 16)
-            int m = 0;
-            for (int t0 = 0; t0 < nw; t0 += 16) {  // (row-uniform)
-                const int t = t0 + sub;
-                const unsigned v = list[min(t, nw - 1)];
-                const float4 rr = rec[v & 0xffffffu];
-                WinEntry e;
-                e.x = rr.x; e.y = rr.y;
-                e.octave = __float_as_int(rr.w) >> 24;
-                const bool inb = t < nw && in_box(e, bx, by, br, minLevel, maxLevel);
-                const unsigned bits = (unsigned)(__ballot(inb) >> rowBase) & 0xffffu;
-                if (inb) list[m + __popc(bits & ((1u << sub) - 1u))] = v;
-                m += __popc(bits);
-            }
-            row_lds_sync();
-            // visit
-            for (int s0 = 0; s0 < m; s0 += 16) {  // (row-uniform)
-                const int sI = s0 + sub;
-                const unsigned v = list[min(sI, m - 1)];
-                const int pos = (int)(v & 0xffffffu);
-                const float4 rr = rec[pos];
-                const uint4 d0 = gd[2 * (size_t)pos], d1 = gd[2 * (size_t)pos + 1];
-                WinEntry e;
-                e.x = rr.x; e.y = rr.y; e.uright = rr.z;
-                const int io = __float_as_int(rr.w);
-                e.idx = io & 0xffffff;
-                e.octave = io >> 24;
-                e.cx = (int)(v >> 24);
-                e.cy = (int)roundf(__fmul_rn(__fsub_rn(rr.y, F.mnMinY), F.invH));
-                e.d[0] = (unsigned long long)d0.x | ((unsigned long long)d0.y << 32);
-                e.d[1] = (unsigned long long)d0.z | ((unsigned long long)d0.w << 32);
-                e.d[2] = (unsigned long long)d1.x | ((unsigned long long)d1.y << 32);
-                e.d[3] = (unsigned long long)d1.z | ((unsigned long long)d1.w << 32);
-                fn(e, sI < m);
-            }
-            row_lds_sync();  // (the next part - or the next window - overwrites the list)
-        }
-    }
-}
+// (row_for_window, the window scan of a row's point through its LDS list: search_dev.h - the Fuse search of kernels_fuse.hip shares it)
 // a candidate key into the point's list: positions by a ballot of the row (n = candidates filed so far, row-uniform)
 __device__ __forceinline__ void row_cache_append(unsigned long long *slot, int &n, bool cand, unsigned long long key, int sub, int rowBase) {
     const unsigned bits = (unsigned)(__ballot(cand) >> rowBase) & 0xffffu;

@@ -1,8 +1,8 @@
 // Device side of the projection searches: what more than one of kernels_search.hip, kernels_search_rows.hip,
-// kernels_resolve.hip, kernels_frame.hip and kernels_reloc.hip uses - a frame's pointers, the candidate key, the claim records of a pass, the
+// kernels_resolve.hip, kernels_frame.hip, kernels_reloc.hip and kernels_fuse.hip uses - a frame's pointers, the candidate key, the claim records of a pass, the
 // meta word of a candidate list, a window's entry, the camera models.  A helper that only one of those files uses lives in
 // that file.  Everything here is __device__ __forceinline__ (or a type) in an anonymous namespace: nothing links across files.
-// Device only: nothing includes this header except those five .hip files.
+// Device only: nothing includes this header except those six .hip files.
 #pragma once
 #include "kb8_math.h"
 #include "ft_search.h"
@@ -390,6 +390,178 @@ __device__ __forceinline__ int predict_scale(float maxDistanceRaw, float dist, f
     if (nScale < 0) nScale = 0;
     else if (nScale >= nLevels) nScale = nLevels - 1;
     return nScale;
+}
+
+// ---- the grid of a frame (k_build_grid, k_build_grid_batch: kernels_frame.hip; k_fuse_grid: kernels_fuse.hip) ----
+// Frame::AssignFeaturesToGrid (src/Frame.cc:409-440) as one CSR per octave: workgroup (octave o, camera) counting-sorts the
+// camera's keypoints of octave o by cell cx * 48 + cy in LDS and files them behind the keypoints of the lower octaves (their
+// number is counted on the way).  An octave outside [0, nlevels) is filed under the nearest bucket; the searches test the
+// keypoint's own octave anyway.  The order inside a cell is free (the searches order candidates by (distance, cx, cy, index)
+// keys).  start: [nlevels][FT_GRID_CELLS + 1] absolute entry positions; rec / desc: the entries (ft_search.h).
+__device__ __forceinline__ void build_grid_body(const FtDevFrame &F, const FramePtrs &Q, int oct, int cam, int *startL, int *startR,
+                                                float4 *recL, uint8_t *descL, float4 *recR, uint8_t *descR) {
+    __shared__ int cnt[FT_GRID_CELLS + 1];
+    __shared__ int wsum[4], wbelow[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = cam == 0 ? (F.Nleft == -1 ? F.N : F.Nleft) : (F.Nleft == -1 ? 0 : F.N - F.Nleft);
+    const ft_keypoint *keys = cam == 0 ? Q.keys : Q.keysR;
+    int *start = (cam == 0 ? startL : startR);
+    if (!start) return;
+    start += (size_t)oct * (FT_GRID_CELLS + 1);
+    for (int c = tid; c <= FT_GRID_CELLS; c += 256) cnt[c] = 0;
+    __syncthreads();
+    auto cellOf = [&](const ft_keypoint &kp) -> int {
+        const int cx = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.mnMinX), F.invW));
+        const int cy = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.mnMinY), F.invH));
+        if (cx < 0 || cx >= FT_GRID_COLS || cy < 0 || cy >= FT_GRID_ROWS) return -1;
+        return cx * FT_GRID_ROWS + cy;
+    };
+    int below = 0;  // keypoints of the grid in lower buckets
+    for (int i = tid; i < n; i += 256) {
+        const ft_keypoint kp = keys[i];
+        const int c = cellOf(kp);
+        if (c < 0) continue;
+        const int bkt = min(max(kp.octave, 0), F.nlevels - 1);
+        if (bkt < oct) below++;
+        else if (bkt == oct) atomicAdd(&cnt[c], 1);
+    }
+    below = wave_sum_i32(below);
+    if (lane == 0) wbelow[wave] = below;
+    __syncthreads();
+    // exclusive scan of the 3072 counts: 12 consecutive cells per thread
+    constexpr int PER = FT_GRID_CELLS / 256;
+    int local = 0;
+    for (int k = 0; k < PER; k++) local += cnt[tid * PER + k];
+    int incl = local;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    const int base = wbelow[0] + wbelow[1] + wbelow[2] + wbelow[3];
+    int run = base + incl - local;
+    for (int w = 0; w < wave; w++) run += wsum[w];
+    const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    for (int k = 0; k < PER; k++) {
+        const int c = tid * PER + k, v = cnt[c];
+        start[c] = run;
+        cnt[c] = run;  // becomes the fill cursor of the cell
+        run += v;
+    }
+    if (tid == 0) start[FT_GRID_CELLS] = base + total;
+    __syncthreads();
+    float4 *rec = cam == 0 ? recL : recR;
+    uint8_t *gdesc = cam == 0 ? descL : descR;
+    const uint8_t *desc = Q.desc + (cam == 0 ? 0 : (size_t)F.Nleft * 32);
+    for (int i = tid; i < n; i += 256) {
+        const ft_keypoint kp = keys[i];
+        const int c = cellOf(kp);
+        if (c < 0 || min(max(kp.octave, 0), F.nlevels - 1) != oct) continue;
+        const int p = atomicAdd(&cnt[c], 1);
+        const float ur = (cam == 0 && F.Nleft == -1 && Q.uright) ? Q.uright[i] : -1.0f;
+        rec[p] = make_float4(kp.x, kp.y, ur, __int_as_float((i & 0xffffff) | (kp.octave << 24)));
+        const uint4 *d = (const uint4 *)(desc + (size_t)i * 32);
+        uint4 *o = (uint4 *)(gdesc + (size_t)p * 32);
+        o[0] = d[0];
+        o[1] = d[1];
+    }
+}
+
+// ---- a map point as a ROW of 16 lanes (kernels_search_rows.hip, kernels_fuse.hip) ----
+__device__ __forceinline__ int row_shfl(int v, int srcLane) { return __shfl(v, srcLane); }
+// The window scan of a row's point, in three steps through a small LDS list of the row (FT_ROW_LIST entries; the lanes of a row
+// belong to one wave, whose LDS operations are served in order - no barrier):
+//   expand  a lane per (octave, column of cells) range, a DPP scan lays the ranges end to end, and every range lane writes the
+//           grid positions of its entries (with the column in the top byte) at their places in the list - where the first form of
+//           this loop looked the range of every entry up again, 16 entries at a time, by a chain of np - 1 shuffles;
+//   filter  16 entries at a time: the 16-byte record, level band and box test of GetFeaturesInArea (in_box), the survivors packed
+//           to the front of the list by a ballot of the row - the cell ranges of a window hold ~2.4 x the keypoints of the box, and
+//           the other 58 % leave here without their descriptor having been loaded;
+//   visit   fn(entry, real) for the survivors, 16 at a time: descriptor, cell row, and whatever the search does with them.
+// Windows with more entries than the list holds go through it in parts.  What fn sees is what it saw before minus the entries
+// in_box rejects (the order inside a list is free).
+#define FT_ROW_LIST 64
+__device__ __forceinline__ void row_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+template <class Fn>
+__device__ __forceinline__ void row_for_window(const FtDevFrame &F, const FramePtrs &Q, int cam, const Window &w, int minLevel, int maxLevel,
+                                               float bx, float by, float br, int sub, int rowBase, unsigned *list, Fn fn) {
+    const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
+    const int lo = checkLevels ? min(max(minLevel, 0), F.nlevels - 1) : 0;
+    const int hi = (checkLevels && maxLevel >= 0) ? min(maxLevel, F.nlevels - 1) : F.nlevels - 1;
+    const int ncolsW = w.maxCX - w.minCX + 1;
+    const int npairs = (hi - lo + 1) * ncolsW;  // (<= 0: an empty band)
+    const int *gs = Q.gridStart[cam];
+    const float4 *rec = Q.gridRec[cam];
+    const uint4 *gd = (const uint4 *)Q.gridDesc[cam];
+    const unsigned colMagic = div_magic_u(ncolsW);
+    for (int p0 = 0; p0 < npairs; p0 += 16) {  // (row-uniform)
+        const int np = min(16, npairs - p0);
+        int b = 0, cnt = 0, myCol = 0;
+        if (sub < np) {
+            const int pidx = p0 + sub;
+            const int oi = colMagic ? (int)__umulhi((unsigned)pidx, colMagic) : pidx;
+            myCol = w.minCX + (pidx - oi * ncolsW);
+            const int *col = gs + (size_t)(lo + oi) * (FT_GRID_CELLS + 1) + myCol * FT_GRID_ROWS;
+            b = col[w.minCY];
+            cnt = col[w.maxCY + 1] - b;
+        }
+        int incl = cnt;  // inclusive scan over the 16 lanes of the row (lanes shifted in from outside the row read 0)
+        incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, true);  // row_shr:1
+        incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, true);  // row_shr:2
+        incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, true);  // row_shr:4
+        incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, true);  // row_shr:8
+        const int total = row_shfl(incl, rowBase + 15);
+        const int start = incl - cnt;
+        const unsigned tag = (unsigned)b | ((unsigned)myCol << 24);  // (grid positions stay below 2^24, columns below 64)
+        for (int w0 = 0; w0 < total; w0 += FT_ROW_LIST) {  // (row-uniform)
+            const int nw = min(FT_ROW_LIST, total - w0);
+            // expand: the part of this lane's range that falls into [w0, w0 + nw)
+            for (int k = max(0, w0 - start), k1 = min(cnt, w0 + nw - start); k < k1; k++) list[start + k - w0] = tag + (unsigned)k;
+            row_lds_sync();
+            // filter: survivors of the box to the front (an entry is read before its group writes, and a group writes below its
+            // own first entry + 16)
+            int m = 0;
+            for (int t0 = 0; t0 < nw; t0 += 16) {  // (row-uniform)
+                const int t = t0 + sub;
+                const unsigned v = list[min(t, nw - 1)];
+                const float4 rr = rec[v & 0xffffffu];
+                WinEntry e;
+                e.x = rr.x; e.y = rr.y;
+                e.octave = __float_as_int(rr.w) >> 24;
+                const bool inb = t < nw && in_box(e, bx, by, br, minLevel, maxLevel);
+                const unsigned bits = (unsigned)(__ballot(inb) >> rowBase) & 0xffffu;
+                if (inb) list[m + __popc(bits & ((1u << sub) - 1u))] = v;
+                m += __popc(bits);
+            }
+            row_lds_sync();
+            // visit
+            for (int s0 = 0; s0 < m; s0 += 16) {  // (row-uniform)
+                const int sI = s0 + sub;
+                const unsigned v = list[min(sI, m - 1)];
+                const int pos = (int)(v & 0xffffffu);
+                const float4 rr = rec[pos];
+                const uint4 d0 = gd[2 * (size_t)pos], d1 = gd[2 * (size_t)pos + 1];
+                WinEntry e;
+                e.x = rr.x; e.y = rr.y; e.uright = rr.z;
+                const int io = __float_as_int(rr.w);
+                e.idx = io & 0xffffff;
+                e.octave = io >> 24;
+                e.cx = (int)(v >> 24);
+                e.cy = (int)roundf(__fmul_rn(__fsub_rn(rr.y, F.mnMinY), F.invH));
+                e.d[0] = (unsigned long long)d0.x | ((unsigned long long)d0.y << 32);
+                e.d[1] = (unsigned long long)d0.z | ((unsigned long long)d0.w << 32);
+                e.d[2] = (unsigned long long)d1.x | ((unsigned long long)d1.y << 32);
+                e.d[3] = (unsigned long long)d1.z | ((unsigned long long)d1.w << 32);
+                fn(e, sI < m);
+            }
+            row_lds_sync();  // (the next part - or the next window - overwrites the list)
+        }
+    }
 }
 
 }  // namespace

@@ -1110,6 +1110,56 @@ def search_for_triangulation(ctx: Context, kf1: TriangKeyFrame, neighbours, pair
     return dict(matches12=m, n=cnt[:nn], best_dist=bd, pairs=out)
 
 
+def inv_level_sigma2(scale_factors):
+    """mvInvLevelSigma2 as ORBextractor builds it: 1.0f / (mvScaleFactor[i] * mvScaleFactor[i])"""
+    sf = np.asarray(scale_factors, np.float32)
+    return (np.float32(1.0) / (sf * sf).astype(np.float32)).astype(np.float32)
+
+
+def fuse_search(ctx: Context, points: dict, targets, want_stage=True):
+    """ORBmatcher::Fuse for one list of map points against every target of a call (ft_fuse_search).
+    points: dict(world_pos [M, 3], normal [M, 3], max_distance, min_distance, descriptors [M, 32]);
+    targets: dicts(kf = FrameView, Tcw = SE3, Ow, log_scale_factor, th, right = False, cam2 = None, valid = None,
+    check_reprojection = True (False: the Sim3 overload), inv_level_sigma2 = None (then from the keyframe's scale factors))
+    -> dict(best_idx [k, M], best_dist [k, M], stage [k, M] or None, n_found [k])"""
+    keep = {}
+
+    def arr(key, a, dt):
+        keep[key] = np.ascontiguousarray(a, dt)
+        return ptr(keep[key])
+
+    M, nt = len(points["world_pos"]), len(targets)
+    P = _capi.FusePoints()
+    P.M = M
+    P.world_pos, P.normal = arr("p", points["world_pos"], np.float32), arr("n", points["normal"], np.float32)
+    P.max_distance, P.min_distance = arr("a", points["max_distance"], np.float32), arr("i", points["min_distance"], np.float32)
+    P.descriptors = arr("d", points["descriptors"], np.uint8)
+    T = (_capi.FuseTarget * max(nt, 1))()
+    for k, t in enumerate(targets):
+        kf = t["kf"]
+        T[k].kf = C.pointer(kf.c)
+        T[k].right = int(bool(t.get("right", False)))
+        cam2 = t.get("cam2")
+        T[k].cam2[:] = [float(v) for v in (list(np.zeros(8) if cam2 is None else cam2) + [0.0] * 8)[:8]]
+        T[k].Tcw = t["Tcw"].c
+        T[k].Ow[:] = [float(v) for v in np.asarray(t["Ow"], np.float32).reshape(3)]
+        T[k].log_scale_factor = float(t["log_scale_factor"])
+        T[k].th = float(t["th"])
+        T[k].check_reprojection = int(bool(t.get("check_reprojection", True)))
+        inv = t.get("inv_level_sigma2")
+        if inv is None and T[k].check_reprojection:
+            inv = inv_level_sigma2(kf.sf)
+        T[k].inv_level_sigma2 = None if inv is None else arr(("s", k), inv, np.float32)
+        T[k].valid = None if t.get("valid") is None else arr(("v", k), t["valid"], np.uint8)
+        assert t.get("valid") is None or len(keep[("v", k)]) == M
+    bi, bd = np.full(max(nt * M, 1), -1, np.int32), np.full(max(nt * M, 1), 256, np.int32)
+    st = np.zeros(max(nt * M, 1), np.uint8) if want_stage else None
+    nf = np.zeros(max(nt, 1), np.int32)
+    check(lib().ft_fuse_search(ctx._h, C.byref(P), nt, T, ptr(bi), ptr(bd), ptr(st), ptr(nf)))
+    return dict(best_idx=bi[:nt * M].reshape(nt, M), best_dist=bd[:nt * M].reshape(nt, M),
+                stage=None if st is None else st[:nt * M].reshape(nt, M), n_found=nf[:nt])
+
+
 def features_in_area(ctx: Context, F: "FrameView", x, y, r, min_level, max_level, right=None, capacity=512):
     """Frame::GetFeaturesInArea for arrays of queries (ft_features_in_area) -> list of index arrays"""
     x = np.ascontiguousarray(x, np.float32); y = np.ascontiguousarray(y, np.float32); r = np.ascontiguousarray(r, np.float32)

@@ -771,6 +771,67 @@ FT_API int ft_search_for_triangulation(ft_context *ctx, const ft_triang_keyframe
                                        int only_stereo, int coarse, int check_orientation, int *matches12 /* n_neighbours x kf1->n */,
                                        int *n_matches /* [n_neighbours] */, int *best_dist /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------------
+ * ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, th, bRight) (src/ORBmatcher.cc:1247-1437) and
+ * ORBmatcher::Fuse(KeyFrame *pKF, Sophus::Sim3f &Scw, vpPoints, th, vpReplacePoint) (:1439-1554): the searches
+ * LocalMapping::SearchInNeighbors runs for each of its 20 - 40 target keyframes and both cameras, then for the current keyframe
+ * (src/LocalMapping.cc:772-803), and LoopClosing::SearchAndFuse for every keyframe of the corrected window (src/LoopClosing.cc:2133,
+ * :2178) - here ONE list of map points against every target (keyframe, camera) of a call.
+ * For point i the reference leaves at the first test that fails; stage[i] reports which (0 = the candidate loop was reached):
+ *   1  !pMP, isBad(), IsInKeyFrame(pKF) / spAlreadyFound.count(pMP) (:1280-1295, :1464): valid[i] == 0
+ *   2  p3Dc = Tcw * p3Dw in the Sophus form (as ft_search_last_frame_se3), p3Dc.z < 0.0f (:1301; z == +-0 passes, invz = 1 / z)
+ *   3  uv = pCamera->project(p3Dc) (cam, or cam2 when right) fails KeyFrame::IsInImage: x >= mnMinX && x < mnMaxX && y >= mnMinY
+ *      && y < mnMaxY (src/KeyFrame.cc:750-753; a NaN fails)
+ *   4  dist3D = (p3Dw - Ow).norm() outside [0.8f * min_distance, 1.2f * max_distance] (:1326)
+ *   5  PO.dot(Pn) < 0.5 * dist3D, compared in double (:1334)
+ *   6  KeyFrame::GetFeaturesInArea(u, v, th * mvScaleFactors[PredictScale(dist3D, pKF)], bRight) is empty (src/KeyFrame.cc:704-748:
+ *      the cells, cell order and box of Frame::GetFeaturesInArea WITHOUT a level filter)
+ * The candidate loop (:1359-1408) keeps the keypoints of octave [level - 1, level]; with check_reprojection those that pass
+ * (double)(e2 * inv_level_sigma2[octave]) > 7.8 where mvuRight[idx] >= 0 (e2 = ex ex + ey ey + er er, ur = u - mbf * invz) or
+ * > 5.99 otherwise (e2 = ex ex + ey ey), every float operation rounded on its own; and takes the smallest DescriptorDistance,
+ * strictly: of equal distances the first in GetFeaturesInArea's order (cell column, cell row, index).  With right the keypoints
+ * are keys_right, the descriptor rows and best_idx are idx + NLeft.
+ * best_idx / best_dist [k * M + i] = bestIdx / bestDist as the loop leaves them for target k: -1 / 256 where no candidate passed or
+ * the point left before the loop (the INT_MAX of the Sim3 overload reads 256 too); n_found[k] = points with best_dist <= TH_LOW (50).
+ * The map bookkeeping behind the loop (Replace, AddObservation, AddMapPoint, vpReplacePoint, :1411-1430) stays with the caller: it
+ * changes nothing a later point's search reads, only which later points test 1 skips - so the caller applies the results in index
+ * order and re-tests 1 at that moment, which is exact for one target.  ACROSS targets MapPoint::Replace recomputes the surviving
+ * point's descriptor (src/MapPoint.cc:297): the call computes, per target, exactly what Fuse computes FOR THE ARRAYS AS GIVEN; a
+ * caller that wants the reference's sequence applies target by target and re-issues a one-target call with valid restricted to the
+ * points whose descriptor or position changed.
+ * Of the keyframe view N, Nleft, the bounds and grid constants, mbf, keys / keys_right, descriptors, uright (Nleft == -1 only),
+ * cam_model, cam, scale_factors and nlevels are read; nothing is written.
+ * Launches per call: 2 whatever n_targets, M and the keyframes hold (every target's grid; every (target, point)), one copy up, one
+ * copy down, one wait; kernel timing names them kernel.fuse_grid / kernel.fuse_search; statistics fuse.total, fuse.launches.
+ * n_targets == 0 or M == 0 returns without a launch (n_found = 0); a target with N == 0 gives -1 / 256 and the stages its points
+ * reach.  FT_ERR_INVALID: null arrays, right on a view with Nleft == -1, an unknown camera model, a keypoint octave outside
+ * [0, nlevels), check_reprojection without inv_level_sigma2, th <= 0, Tcw.q not a unit quaternion.  Limits (FT_ERR_INVALID beyond
+ * them): M < 2^22, n_targets < 2^16, N < 2^24 per keyframe; no other capacity: a window may hold any number of keypoints.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ft_fuse_points { /* shared by all targets of a call */
+    int M;
+    const float *world_pos;     /* M x 3 GetWorldPos() */
+    const float *normal;        /* M x 3 GetNormal() */
+    const float *max_distance;  /* mfMaxDistance (1.2f applied inside, as in ft_map_points) */
+    const float *min_distance;  /* mfMinDistance (0.8f inside) */
+    const uint8_t *descriptors; /* M x 32 GetDescriptor() */
+} ft_fuse_points;
+typedef struct ft_fuse_target {
+    const ft_frame_view *kf;       /* the keyframe as a frame view (see above) */
+    int right;                     /* bRight: project with cam2, search mGridRight / mvKeysRight, bestIdx += NLeft */
+    float cam2[8];                 /* mpCamera2, read when right != 0 */
+    ft_se3 Tcw;                    /* GetPose() / GetRightPose(); Sim3 form: SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) */
+    float Ow[3];                   /* GetCameraCenter() / GetRightCameraCenter(); Sim3 form: Tcw.inverse().translation() */
+    float log_scale_factor;        /* pKF->mfLogScaleFactor */
+    const float *inv_level_sigma2; /* [nlevels] mvInvLevelSigma2, read when check_reprojection != 0 */
+    const uint8_t *valid;          /* [M] test 1 as it stands at call time; NULL = all */
+    float th;                      /* 3.0 in Local Mapping, 4 in Loop Closing */
+    int check_reprojection;        /* 1: Fuse(pKF, vpMapPoints, th, bRight); 0: Fuse(pKF, Scw, ...) (no chi-square test) */
+} ft_fuse_target;
+FT_API int ft_fuse_search(ft_context *ctx, const ft_fuse_points *P, int n_targets, const ft_fuse_target *targets /* [n_targets] */,
+                          int *best_idx /* n_targets x M */, int *best_dist /* n_targets x M */, uint8_t *stage /* n_targets x M, may be NULL */,
+                          int *n_found /* [n_targets] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -594,4 +594,30 @@ inline std::vector<int> SearchForTriangulation(Context &ctx, const ft_triang_key
     return nmatches;
 }
 
+// ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) (src/ORBmatcher.cc:1247-1437) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)
+// (:1439-1554) for one list of map points against every target (keyframe, camera) of LocalMapping::SearchInNeighbors or
+// LoopClosing::SearchAndFuse in one call (ft_fuse_search).  vpMapPoints are the arrays of the points, vTargets one record per
+// Fuse call of the reference's loop (check_reprojection = 1 for the SE3 overload, 0 for the Sim3 one).  bestIdx[k][i] / bestDist[k][i]
+// are the loop's bestIdx / bestDist of point i against target k (-1 / 256: none); the return value counts, per target, the points
+// with bestDist <= TH_LOW.  The bookkeeping behind the loop stays with the caller (INTEGRATION.md has the apply loop).
+inline std::vector<int> Fuse(Context &ctx, const ft_fuse_points &vpMapPoints, const std::vector<ft_fuse_target> &vTargets,
+                             std::vector<std::vector<int>> &bestIdx, std::vector<std::vector<int>> &bestDist,
+                             std::vector<std::vector<uint8_t>> *stage = nullptr) {
+    const size_t nt = vTargets.size(), M = vpMapPoints.M > 0 ? (size_t)vpMapPoints.M : 0;
+    std::vector<int> idx(nt * M + 1, -1), dist(nt * M + 1, 256), nFound(nt + 1, 0);
+    std::vector<uint8_t> st(stage ? nt * M + 1 : 0, 0);
+    check(ft_fuse_search(ctx.handle(), &vpMapPoints, (int)nt, vTargets.data(), idx.data(), dist.data(), stage ? st.data() : nullptr,
+                         nFound.data()));
+    bestIdx.assign(nt, {});
+    bestDist.assign(nt, {});
+    if (stage) stage->assign(nt, {});
+    for (size_t k = 0; k < nt; k++) {
+        bestIdx[k].assign(idx.begin() + k * M, idx.begin() + (k + 1) * M);
+        bestDist[k].assign(dist.begin() + k * M, dist.begin() + (k + 1) * M);
+        if (stage) (*stage)[k].assign(st.begin() + k * M, st.begin() + (k + 1) * M);
+    }
+    nFound.resize(nt);
+    return nFound;
+}
+
 }  // namespace fasttrack
