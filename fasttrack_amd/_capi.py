@@ -100,6 +100,13 @@ class FuseTarget(C.Structure):
                 ("check_reprojection", C.c_int)]
 
 
+class Sim3Job(C.Structure):
+    """ft_sim3_job: one SearchByProjection(pKF, Scw, ...) call against the keyframe of ft_search_keyframe_sim3"""
+    _fields_ = [("points", FusePoints), ("valid", C.c_void_p), ("Tcw", SE3), ("Ow", C.c_float * 3), ("log_scale_factor", C.c_float),
+                ("th", C.c_int), ("ratio_hamming", C.c_float), ("hand_pinhole", C.c_int), ("matched", C.c_void_p),
+                ("point_keypoint", C.c_void_p), ("stage", C.c_void_p), ("n_matches", C.c_int)]
+
+
 class FramePose(C.Structure):
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("tlr", C.c_float * 3)]
 
@@ -265,6 +272,7 @@ def lib() -> C.CDLL:
     L.ft_search_by_bow.argtypes = [vp, C.POINTER(BowSide), vp, C.POINTER(BowSide), i, f, i, vp, ip]
     L.ft_search_for_triangulation.argtypes = [vp, C.POINTER(TriangKeyFrame), i, C.POINTER(TriangKeyFrame), C.POINTER(TriangPair), i, i, i, vp, vp, vp]
     L.ft_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseTarget), vp, vp, vp, vp]
+    L.ft_search_keyframe_sim3.argtypes = [vp, C.POINTER(FrameView), i, C.POINTER(Sim3Job)]
     L.ft_selftest_libm.argtypes = [vp, i, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_ulonglong),
                                    C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]
     L.ft_octree_distribute.argtypes = [vp, i, i, i, i, i, i, vp, i, ip]

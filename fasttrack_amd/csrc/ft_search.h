@@ -390,6 +390,47 @@ struct FtFusePoints {
 int ft_launch_fuse_grid(hipStream_t st, void *arena, const FtFuseTarget *targets, int nTargets, int maxLevels);
 int ft_launch_fuse_search(hipStream_t st, void *arena, const FtFuseTarget *targets, int nTargets, const FtFusePoints &P);
 
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) and its overload with vpPointsKFs / vpMatchedKF
+// (src/ORBmatcher.cc:526-631, :633-745; kernels_sim3.hip) for n_jobs independent searches against ONE keyframe.  A JOB is one call
+// of the reference: its own point list, pose, radius, threshold, projection form and vpMatched.  The keyframe's left camera is a
+// one-camera device frame (F.Nleft == -1, as a Fuse target) handed to the kernels as an argument; every pointer of a job record
+// points into the call's device arena (Rebase).  A candidate is a make_key key of a keypoint that was free on entry, lies in the
+// band [level - 1, level] of the point's window and is no farther than the job's threshold: per point the FT_SIM3_TOP smallest
+// (ascending) and their number.  The resolution scans a point's window again in the rare case that all of its top record is
+// taken and the window holds more, so no list has a capacity.
+#define FT_SIM3_TOP 4
+#define FT_SIM3_NOWRITE 7  // stage: the window held keypoints and the point wrote nothing (0 = it wrote)
+struct FtSim3Proj {
+    float u, v, radius;
+    int level;
+};
+struct FtSim3Job {
+    int M;
+    const float *worldPos, *normal, *maxDist, *minDist;
+    const uint8_t *desc;
+    const uint8_t *valid;  // [M] or null: all
+    FtPose Tcw;            // Sophus form (quat != 0)
+    float Ow[3];
+    float logScaleFactor, th;
+    int thr;          // the largest distance d with (float)d <= TH_LOW * ratioHamming
+    int handPinhole;  // the projection written out by hand (:672-677) instead of mpCamera->project (:564)
+    int wantStage;    // the caller reads stage: tell an empty window (6) from an empty band
+    int *matched;        // [F.N] in / out: -1 = NULL
+    int *pointKeypoint;  // [M]
+    uint8_t *stage;      // [M]
+    int *nMatches;       // [1]
+    FtSim3Proj *proj;         // [M] device only from here on
+    unsigned long long *top;  // [M][FT_SIM3_TOP]
+    int *count;               // [M] candidates of a point
+    int *walk;                // [M] the points with candidates, in index order
+};
+// the three launches of a call, in this order; arena: the call's device arena, jobs: its FtSim3Job[nJobs]
+int ft_launch_sim3_grid(hipStream_t st, const FtDevFrame &F);
+int ft_launch_sim3_candidates(hipStream_t st, const FtDevFrame &F, void *arena, const FtSim3Job *jobs, int nJobs, int maxM);
+int ft_launch_sim3_resolve(hipStream_t st, const FtDevFrame &F, void *arena, const FtSim3Job *jobs, int nJobs);
+// dynamic LDS of the resolution: a taken bit per keypoint (<= FT_INIT_MAX_LDS: 1 228 800 keypoints)
+inline size_t ft_sim3_lds_bytes(int nKeys) { return 4 * (((size_t)nKeys + 31) / 32); }
+
 #ifdef __HIPCC__
 // rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero
 __device__ __forceinline__ int init_bin(float angle1, float angle2) {

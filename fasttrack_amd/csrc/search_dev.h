@@ -1,8 +1,8 @@
 // Device side of the projection searches: what more than one of kernels_search.hip, kernels_search_rows.hip,
-// kernels_resolve.hip, kernels_frame.hip, kernels_reloc.hip and kernels_fuse.hip uses - a frame's pointers, the candidate key, the claim records of a pass, the
+// kernels_resolve.hip, kernels_frame.hip, kernels_reloc.hip, kernels_fuse.hip and kernels_sim3.hip uses - a frame's pointers, the candidate key, the claim records of a pass, the
 // meta word of a candidate list, a window's entry, the camera models.  A helper that only one of those files uses lives in
 // that file.  Everything here is __device__ __forceinline__ (or a type) in an anonymous namespace: nothing links across files.
-// Device only: nothing includes this header except those six .hip files.
+// Device only: nothing includes this header except those seven .hip files.
 #pragma once
 #include "kb8_math.h"
 #include "ft_search.h"

@@ -1160,6 +1160,50 @@ def fuse_search(ctx: Context, points: dict, targets, want_stage=True):
                 stage=None if st is None else st[:nt * M].reshape(nt, M), n_found=nf[:nt])
 
 
+def search_keyframe_sim3(ctx: Context, kf: "FrameView", jobs, want_stage=True, want_point_keypoint=True):
+    """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) and its overload with vpPointsKFs /
+    vpMatchedKF for every job against one keyframe in one call (ft_search_keyframe_sim3).
+    jobs: dicts(points = dict(world_pos [M, 3], normal [M, 3], max_distance, min_distance, descriptors [M, 32]), Tcw = SE3, Ow,
+    log_scale_factor, th (int), ratio_hamming, hand_pinhole = False (True: the overload with vpPointsKFs), valid = None,
+    matched = [N] int32 as on entry (-1 = NULL; not modified))
+    -> list of dict(matched [N], point_keypoint [M] or None, stage [M] or None, n_matches)"""
+    keep = {}
+
+    def arr(key, a, dt):
+        keep[key] = np.ascontiguousarray(a, dt)
+        return ptr(keep[key])
+
+    nj = len(jobs)
+    J = (_capi.Sim3Job * max(nj, 1))()
+    out = []
+    for k, t in enumerate(jobs):
+        pts = t["points"]
+        M = len(pts["world_pos"])
+        P = J[k].points
+        P.M = M
+        P.world_pos, P.normal = arr(("p", k), pts["world_pos"], np.float32), arr(("n", k), pts["normal"], np.float32)
+        P.max_distance, P.min_distance = arr(("a", k), pts["max_distance"], np.float32), arr(("i", k), pts["min_distance"], np.float32)
+        P.descriptors = arr(("d", k), pts["descriptors"], np.uint8)
+        J[k].valid = None if t.get("valid") is None else arr(("v", k), t["valid"], np.uint8)
+        assert t.get("valid") is None or len(keep[("v", k)]) == M
+        J[k].Tcw = t["Tcw"].c
+        J[k].Ow[:] = [float(v) for v in np.asarray(t["Ow"], np.float32).reshape(3)]
+        J[k].log_scale_factor = float(t["log_scale_factor"])
+        J[k].th = int(t["th"])
+        J[k].ratio_hamming = float(t["ratio_hamming"])
+        J[k].hand_pinhole = int(bool(t.get("hand_pinhole", False)))
+        matched = np.array(t["matched"], np.int32, copy=True)
+        assert matched.shape == (kf.c.N,)
+        pk = np.full(max(M, 1), -1, np.int32) if want_point_keypoint else None
+        st = np.zeros(max(M, 1), np.uint8) if want_stage else None
+        J[k].matched, J[k].point_keypoint, J[k].stage = ptr(matched), ptr(pk), ptr(st)
+        J[k].n_matches = -1
+        out.append((matched, pk, st, M))
+    check(lib().ft_search_keyframe_sim3(ctx._h, C.byref(kf.c), nj, J))
+    return [dict(matched=m, point_keypoint=None if pk is None else pk[:M], stage=None if st is None else st[:M], n_matches=int(J[k].n_matches))
+            for k, (m, pk, st, M) in enumerate(out)]
+
+
 def features_in_area(ctx: Context, F: "FrameView", x, y, r, min_level, max_level, right=None, capacity=512):
     """Frame::GetFeaturesInArea for arrays of queries (ft_features_in_area) -> list of index arrays"""
     x = np.ascontiguousarray(x, np.float32); y = np.ascontiguousarray(y, np.float32); r = np.ascontiguousarray(r, np.float32)

@@ -832,6 +832,55 @@ FT_API int ft_fuse_search(ft_context *ctx, const ft_fuse_points *P, int n_target
                           int *best_idx /* n_targets x M */, int *best_dist /* n_targets x M */, uint8_t *stage /* n_targets x M, may be NULL */,
                           int *n_found /* [n_targets] */);
 
+/* ------------------------------------------------------------------------------------------------
+ * ORBmatcher::SearchByProjection(KeyFrame *pKF, Sophus::Sim3f &Scw, vpPoints, vpMatched, th, ratioHamming) (src/ORBmatcher.cc:526-631)
+ * and its overload with vpPointsKFs / vpMatchedKF (:633-745), the matchers behind LoopClosing::FindMatchesByProjection
+ * (src/LoopClosing.cc:755, :777, :964): the map points of a covisibility window projected into ONE keyframe - here n_jobs
+ * independent searches against that keyframe in one call (the loop and the merge detection of NewDetectCommonRegions on the current
+ * keyframe; the candidates of DetectCommonRegionsFromBoW).  A job is one call of the reference.
+ * For point i in index order the reference leaves at the first test that fails; stage[i] reports which, with the codes 1 - 6 of
+ * ft_fuse_search (1 valid[i] == 0: isBad() || spAlreadyFound.count(pMP), the set built from vpMatched ON ENTRY; 2 depth; 3
+ * KeyFrame::IsInImage; 4 distance range; 5 viewing angle; 6 KeyFrame::GetFeaturesInArea(u, v, th * mvScaleFactors[level]) of the
+ * left camera is empty), 7 = the window held keypoints and the point wrote nothing, 0 = the point wrote.  Tests 2 - 5 and the level
+ * are those of the Sim3 overload of Fuse.  hand_pinhole selects the projection: 0 = pKF->mpCamera->project(p3Dc) (:564; cam_model /
+ * cam of the view), 1 = invz = 1 / z, x = X * invz, u = fx * x + cx written out (:672-677; cam[0..3] whatever cam_model is, every
+ * operation rounded on its own) - the only difference between the overloads a search can see; vpMatchedKF[idx] = vpPointsKFs[iMP]
+ * follows from point_keypoint.
+ * Among the window's keypoints with matched[idx] == -1 - on entry, and not written by an earlier point of this job - and octave
+ * in [level - 1, level] the point takes the smallest DescriptorDistance, strictly: of equal distances the first in
+ * GetFeaturesInArea's order (cell column, cell row, index); it writes when (float)bestDist <= (float)TH_LOW * ratio_hamming.  The
+ * host turns that into the integer threshold: the largest d of 0 .. 255 with (float)d <= 50.0f * ratio_hamming.
+ * matched [N] in / out: -1 = NULL on entry, anything else = held; on return the entries this job wrote hold the point's index, every
+ * other entry - all of [Nleft, N) of a two-camera keyframe among them - is unchanged.  point_keypoint[i] (may be NULL) = the
+ * keypoint point i wrote, or -1; n_matches = the return value.  bestDist / bestIdx "as the loop leaves them" are not reported.
+ * Of the keyframe view N, Nleft, the bounds and grid constants, keys, descriptors, cam_model, cam, scale_factors and nlevels are
+ * read; nothing of it is written.
+ * Launches per call: 3 whatever n_jobs and the jobs hold (the keyframe's grid; every (job, point): the tests, the window, the
+ * candidates within the threshold; a workgroup per job walks the points that have candidates in index order), one copy up, one
+ * copy down, one wait; kernel timing names them kernel.sim3_grid / kernel.sim3_candidates / kernel.sim3_resolve; statistics
+ * sim3.total, sim3.launches.  n_jobs == 0, every M == 0, or no left keypoints: no launch, n_matches = 0, matched untouched,
+ * point_keypoint = -1 and stage = 6 (the tests in front of the window are not made).
+ * FT_ERR_INVALID: null arrays, th <= 0, 50 * ratio_hamming < 0 or >= 256 or NaN (the reference would write vpMatched[-1]), Tcw.q
+ * not a unit quaternion, a keypoint octave outside [0, nlevels), an unknown camera model, M >= 2^22, n_jobs >= 2^16, N >= 2^24.
+ * FT_ERR_CAPACITY, with no output written: more than 1 228 800 left keypoints (a taken bit per keypoint in 150 KB of LDS).  No
+ * other capacity: a window may hold any number of candidates.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ft_sim3_job {
+    ft_fuse_points points;    /* vpPoints as arrays */
+    const uint8_t *valid;     /* [M] !isBad() && !spAlreadyFound.count(pMP); NULL = all */
+    ft_se3 Tcw;               /* SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) */
+    float Ow[3];              /* Tcw.inverse().translation() */
+    float log_scale_factor;   /* pKF->mfLogScaleFactor */
+    int th;                   /* 8, 5, 3 in Loop Closing */
+    float ratio_hamming;      /* 1.5, 1.0 */
+    int hand_pinhole;         /* 0: the overload of :526 (mpCamera->project); 1: the overload of :633 (written out) */
+    int *matched;             /* [N] in / out, see above */
+    int *point_keypoint;      /* [M] out, may be NULL */
+    uint8_t *stage;           /* [M] out, may be NULL */
+    int n_matches;            /* out */
+} ft_sim3_job;
+FT_API int ft_search_keyframe_sim3(ft_context *ctx, const ft_frame_view *kf, int n_jobs, ft_sim3_job *jobs /* [n_jobs] */);
+
 #ifdef __cplusplus
 }
 #endif

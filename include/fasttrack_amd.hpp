@@ -620,4 +620,57 @@ inline std::vector<int> Fuse(Context &ctx, const ft_fuse_points &vpMapPoints, co
     return nFound;
 }
 
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (src/ORBmatcher.cc:526-631) on arrays
+// (ft_search_keyframe_sim3 with one job).  Scw is what the reference derives from it: Tcw = SE3f(Scw.rotationMatrix(),
+// Scw.translation() / Scw.scale()) and Ow = Tcw.inverse().translation(); vpPoints the arrays of the points with valid[i] =
+// !isBad() && !spAlreadyFound.count(pMP) (NULL: all); vpMatched holds point indices, -1 = NULL, and receives the index of every
+// point that wrote.  pointKeypoint (may be null) receives the keypoint every point wrote, or -1.  Returns nmatches.
+struct Sim3Pose {
+    ft_se3 Tcw;
+    float Ow[3];
+    float logScaleFactor;  // pKF->mfLogScaleFactor
+};
+inline int SearchByProjection(Context &ctx, const ft_frame_view &pKF, const Sim3Pose &Scw, const ft_fuse_points &vpPoints, const uint8_t *valid,
+                              std::vector<int> &vpMatched, int th, float ratioHamming, std::vector<int> *pointKeypoint = nullptr,
+                              int handPinhole = 0) {
+    ft_sim3_job job = {};
+    job.points = vpPoints;
+    job.valid = valid;
+    job.Tcw = Scw.Tcw;
+    for (int k = 0; k < 3; k++) job.Ow[k] = Scw.Ow[k];
+    job.log_scale_factor = Scw.logScaleFactor;
+    job.th = th;
+    job.ratio_hamming = ratioHamming;
+    job.hand_pinhole = handPinhole;
+    vpMatched.resize(pKF.N > 0 ? (size_t)pKF.N : 0, -1);
+    std::vector<int> none(1, -1);
+    job.matched = vpMatched.empty() ? none.data() : vpMatched.data();
+    if (pointKeypoint) {
+        pointKeypoint->assign(vpPoints.M > 0 ? (size_t)vpPoints.M : 0, -1);
+        job.point_keypoint = pointKeypoint->empty() ? nullptr : pointKeypoint->data();
+    }
+    check(ft_search_keyframe_sim3(ctx.handle(), &pKF, 1, &job));
+    return job.n_matches;
+}
+
+// The overload with vpPointsKFs / vpMatchedKF (:633-745): the projection written out by hand, and vpMatchedKF[idx] = vpPointsKFs[iMP]
+// for every keypoint a point wrote - filled here from the keypoint each point reports.  KF is whatever the caller keeps per point.
+template <class KF>
+inline int SearchByProjection(Context &ctx, const ft_frame_view &pKF, const Sim3Pose &Scw, const ft_fuse_points &vpPoints, const uint8_t *valid,
+                              const std::vector<KF> &vpPointsKFs, std::vector<int> &vpMatched, std::vector<KF> &vpMatchedKF, int th,
+                              float ratioHamming) {
+    std::vector<int> pointKeypoint;
+    const int nmatches = SearchByProjection(ctx, pKF, Scw, vpPoints, valid, vpMatched, th, ratioHamming, &pointKeypoint, 1);
+    vpMatchedKF.resize(vpMatched.size());
+    for (size_t i = 0; i < pointKeypoint.size() && i < vpPointsKFs.size(); i++)
+        if (pointKeypoint[i] >= 0) vpMatchedKF[(size_t)pointKeypoint[i]] = vpPointsKFs[i];
+    return nmatches;
+}
+
+// Every search a caller has against one keyframe in one call: the loop and the merge detection of NewDetectCommonRegions, the
+// candidates of DetectCommonRegionsFromBoW (the jobs' matched / point_keypoint / stage / n_matches are written in place).
+inline void SearchByProjection(Context &ctx, const ft_frame_view &pKF, std::vector<ft_sim3_job> &vJobs) {
+    check(ft_search_keyframe_sim3(ctx.handle(), &pKF, (int)vJobs.size(), vJobs.data()));
+}
+
 }  // namespace fasttrack
