@@ -405,10 +405,8 @@ struct FtSim3Proj {
     int level;
 };
 struct FtSim3Job {
-    int M;
-    const float *worldPos, *normal, *maxDist, *minDist;
-    const uint8_t *desc;
-    const uint8_t *valid;  // [M] or null: all
+    FtFusePoints P;
+    const uint8_t *valid;  // [P.M] or null: all
     FtPose Tcw;            // Sophus form (quat != 0)
     float Ow[3];
     float logScaleFactor, th;
@@ -495,4 +493,17 @@ struct Rebase {
 };
 // (host: what every launch of a batch passes for its arena)
 inline Rebase rebase_of(void *arena) { return Rebase{(uint8_t *)arena, (unsigned long long)(uintptr_t)arena}; }
+// (host) A kernel that takes up to FT_INIT_MAX_LDS of dynamic LDS, more than the default 64 KB, is told so once per device, in
+// front of its launch; the table of the devices that know is the instantiation's, one per kernel.
+template <auto Kernel>
+inline int ft_allow_max_lds() {
+    static int ldsSet[64];
+    int dev = 0;
+    FT_HIP(hipGetDevice(&dev));
+    if (dev >= 0 && dev < 64 && !__atomic_load_n(&ldsSet[dev], __ATOMIC_ACQUIRE)) {
+        FT_HIP(hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FT_INIT_MAX_LDS));
+        __atomic_store_n(&ldsSet[dev], 1, __ATOMIC_RELEASE);
+    }
+    return FT_OK;
+}
 #endif

@@ -10,13 +10,6 @@
 
 namespace {
 
-// the searched camera of a target as a one-camera frame: n keypoints `keys` with descriptor rows `desc`
-struct FuseSide {
-    int n, idxOffset;
-    const ft_keypoint *keys;
-    const uint8_t *desc;
-    const float *uright;  // mvuRight where the keyframe has it (one camera), else null
-};
 struct FuseLayout {
     size_t keys, desc, uright, valid;  // staged
     size_t grid;                       // device only
@@ -24,37 +17,12 @@ struct FuseLayout {
 
 int checkFuseTarget(const ft_fuse_target *t, int k, FuseSide &s) {
     const std::string w = "ft_fuse_search: target " + std::to_string(k) + ": ";
-    const ft_frame_view *F = t->kf;
-    FT_REQUIRE(F, w + "null keyframe view");
-    FT_REQUIRE(F->N >= 0 && F->N < (1 << 24), w + "keypoint count out of range");
-    FT_REQUIRE(F->Nleft == -1 || (F->Nleft >= 0 && F->Nleft <= F->N), w + "Nleft out of range");
-    FT_REQUIRE(!t->right || F->Nleft != -1, w + "right on a keyframe with one camera (Nleft == -1)");
-    FT_REQUIRE(F->cam_model == 0 || F->cam_model == 1, w + "unknown camera model");
-    FT_REQUIRE(F->scale_factors && F->nlevels >= 1 && F->nlevels <= FT_MAX_LEVELS, w + "scale factors missing");
+    const int rc = checkKeyframeSide(t->kf, t->right != 0, w, s);
+    if (rc != FT_OK) return rc;
     FT_REQUIRE(!t->check_reprojection || t->inv_level_sigma2, w + "the reprojection test needs inv_level_sigma2");
     FT_REQUIRE(t->th > 0.f, w + "th must be positive");
-    if (t->right) {
-        s.n = F->N - F->Nleft;
-        s.idxOffset = F->Nleft;
-        s.keys = F->keys_right;
-        s.desc = F->descriptors ? F->descriptors + (size_t)32 * F->Nleft : nullptr;
-        s.uright = nullptr;
-    } else {
-        s.n = F->Nleft == -1 ? F->N : F->Nleft;
-        s.idxOffset = 0;
-        s.keys = F->keys;
-        s.desc = F->descriptors;
-        s.uright = F->Nleft == -1 ? F->uright : nullptr;
-    }
-    FT_REQUIRE(s.n == 0 || (s.keys && s.desc), w + "keypoints or descriptors are null");
-    // the search reads a keypoint's octave back from four bits of its key (make_key, search_dev.h) and indexes inv_level_sigma2 with it
-    for (int i = 0; i < s.n; i++) FT_REQUIRE(s.keys[i].octave >= 0 && s.keys[i].octave < F->nlevels, w + "keypoint octave outside [0, nlevels)");
     return FT_OK;
 }
-
-// the grid of one camera: cell starts per octave, then the entries as 16-byte records and 32-byte descriptors (ft_search.h)
-size_t fuseStartBytes(int nlevels) { return (sizeof(int) * (size_t)nlevels * (FT_GRID_CELLS + 1) + 63) & ~(size_t)63; }
-size_t fuseGridBytes(int nlevels, int n) { return fuseStartBytes(nlevels) + 48 * (size_t)std::max(n, 1); }
 
 }  // namespace
 
@@ -64,24 +32,23 @@ int ft_fuse_search(ft_context *ctx, const ft_fuse_points *P, int n_targets, cons
                    uint8_t *stage, int *n_found) {
     FT_REQUIRE(ctx && P, "ft_fuse_search: null argument");
     FT_REQUIRE(n_targets >= 0 && n_targets < (1 << 16), "ft_fuse_search: n_targets out of range");
+    int rc = checkPoints(*P, "ft_fuse_search: ");
+    if (rc != FT_OK) return rc;
     const int M = P->M;
-    FT_REQUIRE(M >= 0 && M < (1 << 22), "ft_fuse_search: map point count out of range");
-    FT_REQUIRE(M == 0 || (P->world_pos && P->normal && P->max_distance && P->min_distance && P->descriptors),
-               "ft_fuse_search: map point arrays are null");
     FT_REQUIRE(n_targets == 0 || (targets && n_found), "ft_fuse_search: null targets or n_found");
     FT_REQUIRE(n_targets == 0 || M == 0 || (best_idx && best_dist), "ft_fuse_search: null best_idx or best_dist");
     std::vector<FuseSide> sides((size_t)n_targets);
     std::vector<FtPose> poses((size_t)n_targets);
     int maxLevels = 1;
     for (int k = 0; k < n_targets; k++) {
-        int rc = checkFuseTarget(targets + k, k, sides[k]);
+        rc = checkFuseTarget(targets + k, k, sides[k]);
         if (rc == FT_OK) rc = poseOfSe3(&targets[k].Tcw, poses[k]);
         if (rc != FT_OK) return rc;
         maxLevels = std::max(maxLevels, targets[k].kf->nlevels);
     }
     for (int k = 0; k < n_targets; k++) n_found[k] = 0;
     if (n_targets == 0 || M == 0) return FT_OK;
-    int rc = ft_set_device(ctx);
+    rc = ft_set_device(ctx);
     if (rc != FT_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->matchMutex);
     FtTimer tAll;
@@ -89,7 +56,7 @@ int ft_fuse_search(ft_context *ctx, const ft_fuse_points *P, int n_targets, cons
     // best_dist | stage ||| the grids (device only).  One copy up: [0, inputEnd); one copy down: [oFound, outEnd).
     const size_t m = (size_t)M, rows = m * (size_t)n_targets;
     Arena a;
-    const size_t oPos = a.take(12 * m), oNrm = a.take(12 * m), oMaxd = a.take(4 * m), oMind = a.take(4 * m), oDesc = a.take(32 * m);
+    const PointsLayout PL = layoutPoints(a, m);
     std::vector<FuseLayout> L((size_t)n_targets);
     for (int k = 0; k < n_targets; k++) {
         const size_t n = (size_t)std::max(sides[k].n, 1);
@@ -104,15 +71,11 @@ int ft_fuse_search(ft_context *ctx, const ft_fuse_points *P, int n_targets, cons
     const size_t oBestIdx = a.take(4 * rows), oBestDist = a.take(4 * rows);
     const size_t oStage = stage ? a.take(rows) : 0;
     const size_t outEnd = a.off;
-    for (int k = 0; k < n_targets; k++) L[k].grid = a.take(fuseGridBytes(targets[k].kf->nlevels, sides[k].n));
+    for (int k = 0; k < n_targets; k++) L[k].grid = a.take(sideGridBytes(targets[k].kf->nlevels, sides[k].n));
     rc = ft_ensure_scratch(ctx, a.off, outEnd);
     if (rc != FT_OK) return rc;
     uint8_t *pin = (uint8_t *)ctx->scratchPin, *dev = (uint8_t *)ctx->scratchDev;
-    memcpy(pin + oPos, P->world_pos, 12 * m);
-    memcpy(pin + oNrm, P->normal, 12 * m);
-    memcpy(pin + oMaxd, P->max_distance, 4 * m);
-    memcpy(pin + oMind, P->min_distance, 4 * m);
-    memcpy(pin + oDesc, P->descriptors, 32 * m);
+    stagePoints(P, PL, pin);
     FtFuseTarget *recs = (FtFuseTarget *)(pin + oTargets);
     memset(recs, 0, sizeof(FtFuseTarget) * (size_t)n_targets);
     for (int k = 0; k < n_targets; k++) {
@@ -133,11 +96,7 @@ int ft_fuse_search(ft_context *ctx, const ft_fuse_points *P, int n_targets, cons
         R.F.keys = (const ft_keypoint *)(dev + L[k].keys);
         R.F.desc = dev + L[k].desc;
         R.F.uright = s.uright ? (const float *)(dev + L[k].uright) : nullptr;
-        uint8_t *grid = dev + L[k].grid;
-        float4 *rec = (float4 *)(grid + fuseStartBytes(t.kf->nlevels));
-        R.F.gridStart[0] = (const int *)grid;
-        R.F.gridRec[0] = rec;
-        R.F.gridDesc[0] = (const uint8_t *)(rec + std::max(s.n, 1));
+        pointSideGrid(R.F, dev + L[k].grid, t.kf->nlevels, s.n);
         R.Tcw = poses[k];
         memcpy(R.Ow, t.Ow, sizeof R.Ow);
         R.logScaleFactor = t.log_scale_factor;
@@ -152,45 +111,22 @@ int ft_fuse_search(ft_context *ctx, const ft_fuse_points *P, int n_targets, cons
         R.nFound = (int *)(dev + oFound) + k;
     }
     memset(pin + oFound, 0, 4 * (size_t)n_targets);
-    FtFusePoints DP;
-    DP.M = M;
-    DP.worldPos = (const float *)(dev + oPos);
-    DP.normal = (const float *)(dev + oNrm);
-    DP.maxDist = (const float *)(dev + oMaxd);
-    DP.minDist = (const float *)(dev + oMind);
-    DP.desc = dev + oDesc;
+    const FtFusePoints DP = devPoints(M, PL, dev);
     const FtFuseTarget *dTargets = (const FtFuseTarget *)(dev + oTargets);
     hipStream_t st = ctx->stream;
-    FT_HIP(hipMemcpyAsync(dev, pin, inputEnd, hipMemcpyHostToDevice, st));  // one copy: the block is contiguous
-    const bool tm = ctx->kernelTiming;
-    FtEventTimer evt;
-    evt.begin(tm, "kernel.fuse_grid", st);
-    rc = ft_launch_fuse_grid(st, dev, dTargets, n_targets, maxLevels);
-    evt.end(tm, st);
-    if (rc == FT_OK) {
-        evt.begin(tm, "kernel.fuse_search", st);
-        rc = ft_launch_fuse_search(st, dev, dTargets, n_targets, DP);
-        evt.end(tm, st);
-    }
-    if (rc != FT_OK) {
-        hipStreamSynchronize(st);
-        evt.destroy();
-        return rc;
-    }
-    hipError_t e = hipMemcpyAsync(pin + oFound, dev + oFound, outEnd - oFound, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        evt.destroy();
-        FT_HIP(e);
-    }
-    evt.resolve(ctx);
-    evt.destroy();
+    CallEventTimer own;
+    CallScope C{ctx, st, dev, pin, own.evt};
+    C.up(0, inputEnd);  // one copy: the block is contiguous
+    C.launch("kernel.fuse_grid", [&] { return ft_launch_fuse_grid(st, dev, dTargets, n_targets, maxLevels); });
+    C.launch("kernel.fuse_search", [&] { return ft_launch_fuse_search(st, dev, dTargets, n_targets, DP); });
+    rc = C.down(oFound, outEnd);
+    if (rc != FT_OK) return rc;
     memcpy(n_found, pin + oFound, 4 * (size_t)n_targets);
     memcpy(best_idx, pin + oBestIdx, 4 * rows);
     memcpy(best_dist, pin + oBestDist, 4 * rows);
     if (stage) memcpy(stage, pin + oStage, rows);
     ctx->addStat("fuse.total", tAll.ms());
-    ctx->addStat("fuse.launches", 2);
+    ctx->addStat("fuse.launches", C.launches);
     return FT_OK;
 }
 

@@ -29,12 +29,12 @@ InitLayout layoutInit(Arena &a, int N1, int N2, int cap1, int cap2, bool wantDis
     return L;
 }
 
-// S: F2 (with its grid), keys1, desc1, N1, cap1, cap2 and the call's parameters are set; dev / pin: the arena of layout L and
-// its pinned mirror, pin + L.prev already holds vbPrevMatched and is on its way up (or goes up here: prevUp).
-int runInitSearch(ft_context *ctx, hipStream_t st, FtEventTimer &evt, FtInitSearch S, const InitLayout &L, uint8_t *dev, uint8_t *pin,
-                  bool prevUp, float *prev_matched, int *matches12, int *n_matches, int *matched_distance, int N2, int *launches) {
+// S: F2 (with its grid), keys1, desc1, N1, cap1, cap2 and the call's parameters are set; C: the arena of layout L and its pinned
+// mirror, vbPrevMatched is on its way up to L.prev.
+int runInitSearch(CallScope &C, FtInitSearch S, const InitLayout &L, float *prev_matched, int *matches12, int *n_matches,
+                  int *matched_distance, int N2) {
+    uint8_t *dev = C.dev, *pin = C.pin;
     const int N1 = S.N1;
-    if (prevUp) FT_HIP(hipMemcpyAsync(dev + L.prev, pin + L.prev, 8 * (size_t)N1, hipMemcpyHostToDevice, st));
     S.prev = (const float *)(dev + L.prev);
     S.rows = (int *)(dev + L.rows);
     S.ordOfPos = (int *)(dev + L.ordOfPos);
@@ -47,23 +47,11 @@ int runInitSearch(ft_context *ctx, hipStream_t st, FtEventTimer &evt, FtInitSear
     S.nMatches = (int *)(dev + L.tail);
     S.counts = (int *)(dev + L.tail) + 4;
     S.matchedDist = matched_distance ? (int *)(dev + L.dist) : nullptr;
-    const bool tm = ctx->kernelTiming;
-    evt.begin(tm, "kernel.init_prepare", st);
-    int rc = ft_launch_init_prepare(st, S);
-    evt.end(tm, st);
+    C.launch("kernel.init_prepare", [&] { return ft_launch_init_prepare(C.st, S); });
+    C.launch("kernel.init_candidates", [&] { return ft_launch_init_candidates(C.st, S); });
+    C.launch("kernel.init_resolve", [&] { return ft_launch_init_resolve(C.st, S); });
+    const int rc = C.down(L.out, L.outEnd);
     if (rc != FT_OK) return rc;
-    evt.begin(tm, "kernel.init_candidates", st);
-    rc = ft_launch_init_candidates(st, S);
-    evt.end(tm, st);
-    if (rc != FT_OK) return rc;
-    evt.begin(tm, "kernel.init_resolve", st);
-    rc = ft_launch_init_resolve(st, S);
-    evt.end(tm, st);
-    if (rc != FT_OK) return rc;
-    *launches += 3;
-    FT_HIP(hipMemcpyAsync(pin + L.out, dev + L.out, L.outEnd - L.out, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
-    evt.resolve(ctx);
     const int *tail = (const int *)(pin + L.tail);
     FT_REQUIRE(tail[6] == 0, "SearchForInitialization: the keypoint octaves on the device differ from the host's copy of the frame");
     memcpy(matches12, pin + L.matches, 4 * (size_t)N1);
@@ -128,8 +116,9 @@ int ft_search_for_initialization(ft_context *ctx, const ft_frame_view *F1, const
     memcpy(pin + oKeys2, F2->keys, sizeof(ft_keypoint) * (size_t)N2);
     memcpy(pin + oDesc2, F2->descriptors, 32 * (size_t)N2);
     memcpy(pin + L.prev, prev_matched, 8 * (size_t)N1);
-    hipStream_t st = ctx->stream;
-    FT_HIP(hipMemcpyAsync(dev, pin, inputBytes, hipMemcpyHostToDevice, st));
+    CallEventTimer own;
+    CallScope C{ctx, ctx->stream, dev, pin, own.evt};
+    C.up(0, inputBytes);
     FtInitSearch S;
     memset(&S, 0, sizeof S);
     S.F2 = devFrameConstants(F2);
@@ -137,8 +126,7 @@ int ft_search_for_initialization(ft_context *ctx, const ft_frame_view *F1, const
     S.F2.keysR = S.F2.keys;
     S.F2.desc = dev + oDesc2;
     // the grid of F2, whatever option search_grid says for the projection searches: this search walks nothing else
-    rc = launchGrid(st, S.F2, (int *)(dev + oGrid));
-    if (rc != FT_OK) return rc;
+    C.launch(nullptr, [&] { return launchGrid(C.st, S.F2, (int *)(dev + oGrid)); });
     S.keys1 = (const ft_keypoint *)(dev + oKeys1);
     S.desc1 = dev + oDesc1;
     S.N1 = N1;
@@ -147,13 +135,10 @@ int ft_search_for_initialization(ft_context *ctx, const ft_frame_view *F1, const
     S.checkOrientation = check_orientation != 0;
     S.cap1 = cap1;
     S.cap2 = cap2;
-    FtEventTimer evt;
-    int launches = 1;
-    rc = runInitSearch(ctx, st, evt, S, L, dev, pin, false, prev_matched, matches12, n_matches, matched_distance, N2, &launches);
-    evt.destroy();
+    rc = runInitSearch(C, S, L, prev_matched, matches12, n_matches, matched_distance, N2);
     if (rc != FT_OK) return rc;
     ctx->addStat("search_for_initialization.total", tAll.ms());
-    ctx->addStat("search_for_initialization.launches", launches);
+    ctx->addStat("search_for_initialization.launches", C.launches);
     return FT_OK;
 }
 
@@ -178,33 +163,19 @@ int ft_tracked_frame_search_for_initialization(ft_tracked_frame *current, ft_tra
     if (rc != FT_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->matchMutex);
     FtTimer tAll;
-    hipStream_t st = ctx->stream;
     Arena a;
     const InitLayout L = layoutInit(a, N1, N2, cap1, cap2, false);
     ft_tracked_frame *tf = current;
-    if (a.off > tf->initDevBytes || L.outEnd > tf->initPinBytes) {  // grow-only: a stream of frames settles after a few calls
-        FT_HIP(hipStreamSynchronize(st));
-        if (tf->d_init) hipFree(tf->d_init);
-        if (tf->h_init) hipHostFree(tf->h_init);
-        tf->d_init = tf->h_init = nullptr;
-        tf->initDevBytes = tf->initPinBytes = 0;
-        const size_t devBytes = a.off + a.off / 4, pinBytes = L.outEnd + L.outEnd / 4;
-        FT_HIP(hipMalloc((void **)&tf->d_init, devBytes));
-        tf->initDevBytes = devBytes;
-        FT_HIP(hipHostMalloc((void **)&tf->h_init, pinBytes, hipHostMallocDefault));
-        tf->initPinBytes = pinBytes;
-    }
-    uint8_t *dev = tf->d_init, *pin = tf->h_init;
-    memcpy(pin + L.prev, prev_matched, 8 * (size_t)N1);
+    rc = ensureInitArena(tf, a.off, L.outEnd);
+    if (rc != FT_OK) return rc;
+    CallScope C{ctx, ctx->stream, tf->d_init, tf->h_init, tf->evt};
+    memcpy(C.pin + L.prev, prev_matched, 8 * (size_t)N1);
+    C.up(L.prev, L.prev + 8 * (size_t)N1);
     FtInitSearch S;
     memset(&S, 0, sizeof S);
     S.F2 = current->DF;
-    int launches = 0;
-    if (!S.F2.gridStart[0]) {  // option search_grid = 0 when the frame was loaded: the grid for this call
-        rc = launchGrid(st, S.F2, tf->d_grid);
-        if (rc != FT_OK) return rc;
-        launches++;
-    }
+    // option search_grid = 0 when the frame was loaded: the grid for this call
+    if (!S.F2.gridStart[0]) C.launch(nullptr, [&] { return launchGrid(C.st, S.F2, tf->d_grid); });
     S.keys1 = initial->DF.keys;
     S.desc1 = initial->DF.desc;
     S.N1 = N1;
@@ -213,10 +184,10 @@ int ft_tracked_frame_search_for_initialization(ft_tracked_frame *current, ft_tra
     S.checkOrientation = check_orientation != 0;
     S.cap1 = cap1;
     S.cap2 = cap2;
-    rc = runInitSearch(ctx, st, tf->evt, S, L, dev, pin, true, prev_matched, matches12, n_matches, nullptr, N2, &launches);
+    rc = runInitSearch(C, S, L, prev_matched, matches12, n_matches, nullptr, N2);
     if (rc != FT_OK) return rc;
     ctx->addStat("tracked.search_for_initialization.total", tAll.ms());
-    ctx->addStat("tracked.search_for_initialization.launches", launches);
+    ctx->addStat("tracked.search_for_initialization.launches", C.launches);
     return FT_OK;
 }
 

@@ -13,7 +13,6 @@
 //                  computes them), then the window in the grid with the level band as the scan's octave range
 //                  (row_for_window, search_dev.h), the chi-square test, the Hamming distance; the row minimum of the key
 //                  (distance, cell x, cell y, index) is the reference's strict `dist < bestDist` over GetFeaturesInArea's order.
-//                  FT_FUSE_ROWS=0 builds the wave-per-point form over for_window instead (EXPERIMENTS.md section 19).
 // Two launches per call, whatever the number of targets and points.  blockIdx.y is the target: everything a workgroup reads of
 // it sits at a uniform address (scalar loads).
 #include <algorithm>
@@ -21,10 +20,6 @@
 #include "search_dev.h"
 
 namespace {
-
-#ifndef FT_FUSE_ROWS
-#define FT_FUSE_ROWS 1
-#endif
 
 __global__ __launch_bounds__(256) void k_fuse_grid(const FtFuseTarget *__restrict__ targets, Rebase rb) {
     const FtDevFrame &F = targets[blockIdx.y].F;
@@ -97,7 +92,6 @@ __device__ __forceinline__ void fuse_store(const FtFuseTarget &T, const Rebase &
     if (bd <= FT_TH_LOW) atomicAdd(rb(T.nFound), 1);
 }
 
-#if FT_FUSE_ROWS
 #define FT_FUSE_PPB 16  // points per workgroup: 4 waves x 4 rows
 __global__ __launch_bounds__(256) void k_fuse_search(const FtFuseTarget *__restrict__ targets, Rebase rb, FtFusePoints P) {
     __shared__ unsigned rowLists[FT_FUSE_PPB][FT_ROW_LIST];
@@ -116,10 +110,7 @@ __global__ __launch_bounds__(256) void k_fuse_search(const FtFuseTarget *__restr
         bool any = false;
         if (!w.empty) {
             unsigned long long q[4];
-            {
-                const unsigned long long *d = (const unsigned long long *)(P.desc + (size_t)i * 32);
-                q[0] = d[0]; q[1] = d[1]; q[2] = d[2]; q[3] = d[3];
-            }
+            load_desc256(P.desc, i, q);
             const int level = p.level, check = T.checkReproj;
             const float invLo = T.invSigma2[max(level - 1, 0)], invHi = T.invSigma2[level];
             // the band [level - 1, level] (:1368) is the scan's octave range: what reaches the visitor passed band and box
@@ -142,47 +133,6 @@ __global__ __launch_bounds__(256) void k_fuse_search(const FtFuseTarget *__restr
     }
     if (sub == 0) fuse_store(T, rb, i, stage, k0);
 }
-#else
-#define FT_FUSE_PPB 4  // a wave per point
-__global__ __launch_bounds__(256) void k_fuse_search(const FtFuseTarget *__restrict__ targets, Rebase rb, FtFusePoints P) {
-    const int lane = threadIdx.x & 63;
-    const int i = (int)blockIdx.x * FT_FUSE_PPB + wave_index();
-    if (i >= P.M) return;
-    const FtFuseTarget &T = targets[blockIdx.y];
-    const FtDevFrame &F = T.F;
-    const FramePtrs Q = frame_ptrs(F, rb);
-    const FusePoint p = fuse_point(T, rb(T.valid), P, i);
-    int stage = p.stage;
-    unsigned long long k0 = KEY_NONE;
-    if (stage == FT_FUSE_SEARCHED) {
-        const Window w = cell_window(F, p.u, p.v, p.radius);
-        bool any = false;
-        if (!w.empty) {
-            const unsigned long long *d = (const unsigned long long *)(P.desc + (size_t)i * 32);
-            const unsigned long long q[4] = {d[0], d[1], d[2], d[3]};
-            const int level = p.level, check = T.checkReproj;
-            const float invLo = T.invSigma2[max(level - 1, 0)], invHi = T.invSigma2[level];
-            for_window(F, Q, 0, Q.keys, F.N, w, level - 1, level, lane, [&](const WinEntry &kp) {
-                if (!in_box(kp, p.u, p.v, p.radius, level - 1, level)) return;
-                any = true;
-                if (check && !fuse_reprojects(p, kp, kp.octave == level ? invHi : invLo)) return;
-                const unsigned long long key = make_key(hamming256(q, kp.d), kp.cx, kp.cy, kp.idx, kp.octave, false);
-                k0 = key < k0 ? key : k0;
-            });
-            any = __ballot(any) != 0ull;
-            if (!any && T.stage) {
-                for_window(F, Q, 0, Q.keys, F.N, w, -1, -1, lane, [&](const WinEntry &kp) {
-                    if (in_box(kp, p.u, p.v, p.radius, -1, -1)) any = true;
-                });
-                any = __ballot(any) != 0ull;
-            }
-        }
-        if (!any) stage = FT_FUSE_EMPTY;
-        k0 = wave_min_u64(k0);
-    }
-    if (lane == 0) fuse_store(T, rb, i, stage, k0);
-}
-#endif
 
 }  // namespace
 

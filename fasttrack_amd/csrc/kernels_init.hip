@@ -113,8 +113,8 @@ __global__ __launch_bounds__(64 * FT_INIT_WPB) void k_init_candidates(FtInitSear
     if (row >= n1) return;
     const int i1 = __builtin_amdgcn_readfirstlane(S.rows[row]);
     const float x = S.prev[2 * (size_t)i1], y = S.prev[2 * (size_t)i1 + 1], r = S.window;
-    const unsigned long long *dp = (const unsigned long long *)(S.desc1 + (size_t)i1 * 32);
-    const unsigned long long d1[4] = {dp[0], dp[1], dp[2], dp[3]};
+    unsigned long long d1[4];
+    load_desc256(S.desc1, i1, d1);
     const FtDevFrame &F = S.F2;
     const int *gs = F.gridStart[0];
     const float4 *rec = F.gridRec[0];
@@ -360,13 +360,8 @@ int ft_launch_init_resolve(hipStream_t st, const FtInitSearch &S) {
         ft_set_error("SearchForInitialization: the level-0 keypoints of the two frames exceed the LDS tables of the resolution");
         return FT_ERR_CAPACITY;
     }
-    static int ldsSet[64];  // per device: the kernel may use more than the default 64 KB of dynamic LDS
-    int dev = 0;
-    FT_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !__atomic_load_n(&ldsSet[dev], __ATOMIC_ACQUIRE)) {
-        FT_HIP(hipFuncSetAttribute((const void *)k_init_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, FT_INIT_MAX_LDS));
-        __atomic_store_n(&ldsSet[dev], 1, __ATOMIC_RELEASE);
-    }
+    const int rc = ft_allow_max_lds<k_init_resolve>();
+    if (rc != FT_OK) return rc;
     hipLaunchKernelGGL(k_init_resolve, dim3(1), dim3(FT_INIT_RES_T), lds, st, S);
     FT_HIP(hipGetLastError());
     return FT_OK;

@@ -66,16 +66,6 @@ __global__ __launch_bounds__(256) void k_reloc_project(FtRelocSearch S) {
     S.proj[i] = pj;
 }
 
-// key joins the ascending t[0 .. FT_RELOC_TOP)
-__device__ __forceinline__ void reloc_top_insert(unsigned long long t[FT_RELOC_TOP], unsigned long long key) {
-#pragma unroll
-    for (int k = 0; k < FT_RELOC_TOP; k++) {
-        const unsigned long long lo = key < t[k] ? key : t[k];
-        key = key < t[k] ? t[k] : key;
-        t[k] = lo;
-    }
-}
-
 __global__ __launch_bounds__(64 * FT_RELOC_WPB) void k_reloc_candidates(FtRelocSearch S) {
     __shared__ int counter[FT_RELOC_WPB];
     const int lane = threadIdx.x & 63, wave = wave_index();
@@ -94,8 +84,8 @@ __global__ __launch_bounds__(64 * FT_RELOC_WPB) void k_reloc_candidates(FtRelocS
         const float radius = __fmul_rn(S.th, F.sf[level]);
         const Window w = cell_window(F, u, v, radius);
         if (!w.empty) {
-            const unsigned long long *dp = (const unsigned long long *)(S.desc + (size_t)i * 32);
-            const unsigned long long d1[4] = {dp[0], dp[1], dp[2], dp[3]};
+            unsigned long long d1[4];
+            load_desc256(S.desc, i, d1);
             unsigned long long *seg = S.seg + (size_t)i * FT_RELOC_SEG;
             int *ctr = &counter[wave];
             if (lane == 0) *ctr = 0;
@@ -108,7 +98,7 @@ __global__ __launch_bounds__(64 * FT_RELOC_WPB) void k_reloc_candidates(FtRelocS
                 const unsigned long long key = make_key(hamming256(d1, kp.d), kp.cx, kp.cy, kp.idx, kp.octave, false);
                 const int at = atomicAdd(ctr, 1);
                 if (at < FT_RELOC_SEG) seg[at] = key;
-                reloc_top_insert(t, key);
+                top_insert<FT_RELOC_TOP>(t, key);
             });
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -271,13 +261,8 @@ int ft_launch_reloc_resolve(hipStream_t st, const FtRelocSearch &S) {
         ft_set_error("SearchByProjection(Frame, KeyFrame): keypoints and points exceed the LDS tables of the resolution");
         return FT_ERR_CAPACITY;
     }
-    static int ldsSet[64];  // per device: the kernel may use more than the default 64 KB of dynamic LDS
-    int dev = 0;
-    FT_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !__atomic_load_n(&ldsSet[dev], __ATOMIC_ACQUIRE)) {
-        FT_HIP(hipFuncSetAttribute((const void *)k_reloc_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, FT_INIT_MAX_LDS));
-        __atomic_store_n(&ldsSet[dev], 1, __ATOMIC_RELEASE);
-    }
+    const int rc = ft_allow_max_lds<k_reloc_resolve>();
+    if (rc != FT_OK) return rc;
     hipLaunchKernelGGL(k_reloc_resolve, dim3(1), dim3(FT_RELOC_RES_T), lds, st, S);
     FT_HIP(hipGetLastError());
     return FT_OK;

@@ -45,7 +45,7 @@ __device__ __forceinline__ Sim3Point sim3_point(const FtDevFrame &F, const FtSim
     r.u = r.v = r.radius = 0.f;
     const uint8_t *valid = rb(J.valid);
     if (valid && !valid[i]) return r;  // isBad() || spAlreadyFound.count(pMP)
-    const float *wp = rb(J.worldPos) + 3 * (size_t)i;
+    const float *wp = rb(J.P.worldPos) + 3 * (size_t)i;
     const float xw[3] = {wp[0], wp[1], wp[2]};
     float xc[3], uv[2];
     transform_pose(J.Tcw.m, J.Tcw.q, 1, xw, xc);
@@ -65,11 +65,11 @@ __device__ __forceinline__ Sim3Point sim3_point(const FtDevFrame &F, const FtSim
     if (!(uv[0] >= F.mnMinX && uv[0] < F.mnMaxX && uv[1] >= F.mnMinY && uv[1] < F.mnMaxY)) return r;
     const float PO[3] = {__fsub_rn(xw[0], J.Ow[0]), __fsub_rn(xw[1], J.Ow[1]), __fsub_rn(xw[2], J.Ow[2])};
     const float dist3D = norm3(PO);
-    const float maxRaw = rb(J.maxDist)[i];
-    const float maxDistance = __fmul_rn(1.2f, maxRaw), minDistance = __fmul_rn(0.8f, rb(J.minDist)[i]);
+    const float maxRaw = rb(J.P.maxDist)[i];
+    const float maxDistance = __fmul_rn(1.2f, maxRaw), minDistance = __fmul_rn(0.8f, rb(J.P.minDist)[i]);
     r.stage = FT_FUSE_DISTANCE;
     if (dist3D < minDistance || dist3D > maxDistance) return r;
-    const float *np = rb(J.normal) + 3 * (size_t)i;
+    const float *np = rb(J.P.normal) + 3 * (size_t)i;
     const float Pn[3] = {np[0], np[1], np[2]};
     r.stage = FT_FUSE_NORMAL;
     if ((double)dot3(PO, Pn) < 0.5 * (double)dist3D) return r;  // `PO.dot(Pn)<0.5*dist`: the float dot against a double product
@@ -81,25 +81,6 @@ __device__ __forceinline__ Sim3Point sim3_point(const FtDevFrame &F, const FtSim
     return r;
 }
 
-// key joins the ascending t[0 .. FT_SIM3_TOP)
-__device__ __forceinline__ void sim3_top_insert(unsigned long long t[FT_SIM3_TOP], unsigned long long key) {
-#pragma unroll
-    for (int k = 0; k < FT_SIM3_TOP; k++) {
-        const unsigned long long lo = key < t[k] ? key : t[k];
-        key = key < t[k] ? t[k] : key;
-        t[k] = lo;
-    }
-}
-
-// sum over the 16 lanes of a row, in every lane of it
-__device__ __forceinline__ int row_sum_i32(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);  // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);  // row_mirror
-    return v;
-}
-
 #define FT_SIM3_PPB 16  // points per workgroup: 4 waves x 4 rows
 __global__ __launch_bounds__(256) void k_sim3_candidates(const FtDevFrame F, const FtSim3Job *__restrict__ jobs, Rebase rb) {
     __shared__ unsigned rowLists[FT_SIM3_PPB][FT_ROW_LIST];
@@ -107,7 +88,7 @@ __global__ __launch_bounds__(256) void k_sim3_candidates(const FtDevFrame F, con
     const int lane = threadIdx.x & 63, sub = lane & 15, rowBase = lane & 48;
     const int i = (int)blockIdx.x * FT_SIM3_PPB + (int)(threadIdx.x >> 4);
     const FtSim3Job &J = jobs[blockIdx.y];
-    if (i >= J.M) return;
+    if (i >= J.P.M) return;
     const FramePtrs Q = frame_ptrs(F, FT_NO_REBASE);
     const Sim3Point p = sim3_point(F, J, rb, i);
     int stage = p.stage, count = 0;
@@ -119,10 +100,7 @@ __global__ __launch_bounds__(256) void k_sim3_candidates(const FtDevFrame F, con
         bool any = false;
         if (!w.empty) {
             unsigned long long q[4];
-            {
-                const unsigned long long *d = (const unsigned long long *)(rb(J.desc) + (size_t)i * 32);
-                q[0] = d[0]; q[1] = d[1]; q[2] = d[2]; q[3] = d[3];
-            }
+            load_desc256(rb(J.P.desc), i, q);
             const int level = p.level, thr = J.thr;
             const int *matched = rb(J.matched);
             // the band [level - 1, level] (:608) is the scan's octave range: what reaches the visitor passed band and box
@@ -131,7 +109,7 @@ __global__ __launch_bounds__(256) void k_sim3_candidates(const FtDevFrame F, con
                 const int dist = hamming256(q, kp.d);
                 // `if(vpMatched[idx]) continue;` as far as the entry state decides it; `bestDist<=TH_LOW*ratioHamming` (:622)
                 if (real && dist <= thr && matched[kp.idx] == -1) {
-                    sim3_top_insert(t, make_key(dist, kp.cx, kp.cy, kp.idx, kp.octave, false));
+                    top_insert<FT_SIM3_TOP>(t, make_key(dist, kp.cx, kp.cy, kp.idx, kp.octave, false));
                     count++;
                 }
             });
@@ -176,7 +154,7 @@ __global__ __launch_bounds__(FT_SIM3_RES_T) void k_sim3_resolve(const FtDevFrame
     __shared__ int waveCnt[FT_SIM3_RES_T / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
     const FtSim3Job &J = jobs[blockIdx.y];
-    const int M = J.M, nKeys = F.N;
+    const int M = J.P.M, nKeys = F.N;
     const int nWords = (nKeys + 31) / 32;
     unsigned *taken = sim3_taken;
     for (int k = tid; k < nWords; k += FT_SIM3_RES_T) taken[k] = 0u;
@@ -265,7 +243,7 @@ __global__ __launch_bounds__(FT_SIM3_RES_T) void k_sim3_resolve(const FtDevFrame
                 const int pt = __builtin_amdgcn_readlane(curPt, j);
                 const FtSim3Proj pj = proj[pt];
                 const Window w = cell_window(F, pj.u, pj.v, pj.radius);
-                const unsigned long long *dp = (const unsigned long long *)(rb(J.desc) + (size_t)pt * 32);
+                const unsigned long long *dp = (const unsigned long long *)(rb(J.P.desc) + (size_t)pt * 32);
                 const unsigned long long d1[4] = {dp[0], dp[1], dp[2], dp[3]};
                 unsigned long long k0 = KEY_NONE;
                 for_window(F, Q, 0, Q.keys, nKeys, w, pj.level - 1, pj.level, lane, [&](const WinEntry &kp) {
@@ -323,13 +301,8 @@ int ft_launch_sim3_resolve(hipStream_t st, const FtDevFrame &F, void *arena, con
         ft_set_error("SearchByProjection(KeyFrame, Sim3): the keyframe's keypoints exceed the taken bits of the resolution");
         return FT_ERR_CAPACITY;
     }
-    static int ldsSet[64];  // per device: the kernel may use more than the default 64 KB of dynamic LDS
-    int dev = 0;
-    FT_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !__atomic_load_n(&ldsSet[dev], __ATOMIC_ACQUIRE)) {
-        FT_HIP(hipFuncSetAttribute((const void *)k_sim3_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, FT_INIT_MAX_LDS));
-        __atomic_store_n(&ldsSet[dev], 1, __ATOMIC_RELEASE);
-    }
+    const int rc = ft_allow_max_lds<k_sim3_resolve>();
+    if (rc != FT_OK) return rc;
     hipLaunchKernelGGL(k_sim3_resolve, dim3(1, nJobs), dim3(FT_SIM3_RES_T), lds, st, F, jobs, rebase_of(arena));
     FT_HIP(hipGetLastError());
     return FT_OK;

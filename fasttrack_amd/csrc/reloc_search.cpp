@@ -71,13 +71,13 @@ int checkRelocCaps(int nLeft, int M) {
     return FT_OK;
 }
 
-// S: F (with its grid), holder and the call's parameters are set; dev / pin: the arena of layout L and its pinned mirror, the
-// points are staged in pin.  Returns with assign / best / tail in pin; FT_ERR_CAPACITY (nothing written, the device's holder_obs
-// included) when a point's candidates exceed its segment.
-int runRelocSearch(ft_context *ctx, hipStream_t st, FtEventTimer &evt, FtRelocSearch S, const RelocLayout &L, uint8_t *dev, uint8_t *pin,
-                   bool wantBest, int *launches) {
-    FT_HIP(hipMemcpyAsync(dev + L.valid, pin + L.valid, L.inputEnd - L.valid, hipMemcpyHostToDevice, st));
-    FT_HIP(hipMemsetAsync(dev + L.tail, 0, 64, st));
+// S: F (with its grid), holder and the call's parameters are set; C: the arena of layout L and its pinned mirror, the points are
+// staged in pin.  Returns with assign / best / tail in pin; FT_ERR_CAPACITY (nothing written, the device's holder_obs included)
+// when a point's candidates exceed its segment.
+int runRelocSearch(CallScope &C, FtRelocSearch S, const RelocLayout &L, bool wantBest) {
+    uint8_t *dev = C.dev;
+    C.up(L.valid, L.inputEnd);
+    C.zero(L.tail, L.tail + 64);
     S.valid = dev + L.valid;
     S.worldPos = (const float *)(dev + L.pos);
     S.maxDist = (const float *)(dev + L.maxd);
@@ -94,25 +94,12 @@ int runRelocSearch(ft_context *ctx, hipStream_t st, FtEventTimer &evt, FtRelocSe
     S.bestIdx = wantBest ? (int *)(dev + L.bestIdx) : nullptr;
     S.nMatches = (int *)(dev + L.tail);
     S.status = (int *)(dev + L.tail) + 4;
-    const bool tm = ctx->kernelTiming;
-    evt.begin(tm, "kernel.reloc_project", st);
-    int rc = ft_launch_reloc_project(st, S);
-    evt.end(tm, st);
+    C.launch("kernel.reloc_project", [&] { return ft_launch_reloc_project(C.st, S); });
+    C.launch("kernel.reloc_candidates", [&] { return ft_launch_reloc_candidates(C.st, S); });
+    C.launch("kernel.reloc_resolve", [&] { return ft_launch_reloc_resolve(C.st, S); });
+    const int rc = C.down(L.out, L.outEnd);
     if (rc != FT_OK) return rc;
-    evt.begin(tm, "kernel.reloc_candidates", st);
-    rc = ft_launch_reloc_candidates(st, S);
-    evt.end(tm, st);
-    if (rc != FT_OK) return rc;
-    evt.begin(tm, "kernel.reloc_resolve", st);
-    rc = ft_launch_reloc_resolve(st, S);
-    evt.end(tm, st);
-    if (rc != FT_OK) return rc;
-    *launches += 3;
-    FT_HIP(hipMemcpyAsync(pin + L.out, dev + L.out, L.outEnd - L.out, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
-    evt.resolve(ctx);
-    const int *tail = (const int *)(pin + L.tail);
-    if (tail[4] != 0) {
+    if (((const int *)(C.pin + L.tail))[4] != 0) {
         ft_set_error("SearchByProjection(Frame, KeyFrame): a point's window holds more than 256 free keypoints of its level band");
         return FT_ERR_CAPACITY;
     }
@@ -171,14 +158,14 @@ int ft_search_keyframe_projection(ft_context *ctx, ft_frame_view *Cur, const ft_
     uint8_t *pin = (uint8_t *)ctx->scratchPin, *dev = (uint8_t *)ctx->scratchDev;
     stageFrame(Cur, FL, pin);
     stageReloc(K, check_orientation != 0, L, pin);
-    hipStream_t st = ctx->stream;
-    FT_HIP(hipMemcpyAsync(dev, pin, frameBytes, hipMemcpyHostToDevice, st));
+    CallEventTimer own;
+    CallScope C{ctx, ctx->stream, dev, pin, own.evt};
+    C.up(0, frameBytes);
     FtRelocSearch S;
     memset(&S, 0, sizeof S);
     S.F = devFrame(Cur, FL, dev);
     // the grid of the frame, whatever option search_grid says for the other projection searches: this one walks nothing else
-    rc = launchGrid(st, S.F, (int *)(dev + oGrid));
-    if (rc != FT_OK) return rc;
+    C.launch(nullptr, [&] { return launchGrid(C.st, S.F, (int *)(dev + oGrid)); });
     S.N = M;
     S.Tcw = pose;
     S.logScaleFactor = log_scale_factor;
@@ -186,10 +173,7 @@ int ft_search_keyframe_projection(ft_context *ctx, ft_frame_view *Cur, const ft_
     S.orbDist = orb_dist;
     S.checkOrientation = check_orientation != 0;
     S.holder = (int *)(dev + FL.holder);
-    FtEventTimer evt;
-    int launches = 1;
-    rc = runRelocSearch(ctx, st, evt, S, L, dev, pin, wantBest, &launches);
-    evt.destroy();
+    rc = runRelocSearch(C, S, L, wantBest);
     if (rc != FT_OK) return rc;
     memcpy(assign, pin + L.assign, 4 * (size_t)N);
     if (best_dist) memcpy(best_dist, pin + L.bestDist, 4 * (size_t)M);
@@ -197,7 +181,7 @@ int ft_search_keyframe_projection(ft_context *ctx, ft_frame_view *Cur, const ft_
     if (n_matches) *n_matches = *(const int *)(pin + L.tail);
     applyAssign(assign, N, K->observations, Cur->holder_obs);
     ctx->addStat("search_keyframe_projection.total", tAll.ms());
-    ctx->addStat("search_keyframe_projection.launches", launches);
+    ctx->addStat("search_keyframe_projection.launches", C.launches);
     return FT_OK;
 }
 
@@ -223,32 +207,17 @@ int ft_tracked_frame_search_keyframe_projection(ft_tracked_frame *tf, const ft_k
     if (rc != FT_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->matchMutex);
     FtTimer tAll;
-    hipStream_t st = ctx->stream;
     Arena a;
     const RelocLayout L = layoutReloc(a, M, N, false);
-    if (a.off > tf->initDevBytes || L.outEnd > tf->initPinBytes) {  // grow-only: a stream of frames settles after a few calls
-        FT_HIP(hipStreamSynchronize(st));
-        if (tf->d_init) hipFree(tf->d_init);
-        if (tf->h_init) hipHostFree(tf->h_init);
-        tf->d_init = tf->h_init = nullptr;
-        tf->initDevBytes = tf->initPinBytes = 0;
-        const size_t devBytes = a.off + a.off / 4, pinBytes = L.outEnd + L.outEnd / 4;
-        FT_HIP(hipMalloc((void **)&tf->d_init, devBytes));
-        tf->initDevBytes = devBytes;
-        FT_HIP(hipHostMalloc((void **)&tf->h_init, pinBytes, hipHostMallocDefault));
-        tf->initPinBytes = pinBytes;
-    }
-    uint8_t *dev = tf->d_init, *pin = tf->h_init;
-    stageReloc(K, check_orientation != 0, L, pin);
+    rc = ensureInitArena(tf, a.off, L.outEnd);
+    if (rc != FT_OK) return rc;
+    CallScope C{ctx, ctx->stream, tf->d_init, tf->h_init, tf->evt};
+    stageReloc(K, check_orientation != 0, L, C.pin);
     FtRelocSearch S;
     memset(&S, 0, sizeof S);
     S.F = tf->DF;
-    int launches = 0;
-    if (!S.F.gridStart[0]) {  // option search_grid = 0 when the frame was loaded: the grid for this call
-        rc = launchGrid(st, S.F, tf->d_grid);
-        if (rc != FT_OK) return rc;
-        launches++;
-    }
+    // option search_grid = 0 when the frame was loaded: the grid for this call
+    if (!S.F.gridStart[0]) C.launch(nullptr, [&] { return launchGrid(C.st, S.F, tf->d_grid); });
     S.N = M;
     S.Tcw = pose;
     S.logScaleFactor = log_scale_factor;
@@ -256,13 +225,13 @@ int ft_tracked_frame_search_keyframe_projection(ft_tracked_frame *tf, const ft_k
     S.orbDist = orb_dist;
     S.checkOrientation = check_orientation != 0;
     S.holder = tf->d_holder;  // the resident occupancy, updated where it is: the next search on this frame sees it
-    rc = runRelocSearch(ctx, st, tf->evt, S, L, dev, pin, false, &launches);
+    rc = runRelocSearch(C, S, L, false);
     if (rc != FT_OK) return rc;
-    memcpy(assign, pin + L.assign, 4 * (size_t)N);
-    if (n_matches) *n_matches = *(const int *)(pin + L.tail);
+    memcpy(assign, C.pin + L.assign, 4 * (size_t)N);
+    if (n_matches) *n_matches = *(const int *)(C.pin + L.tail);
     applyAssign(assign, N, K->observations, tf->holder.data());
     ctx->addStat("tracked.search_keyframe_projection.total", tAll.ms());
-    ctx->addStat("tracked.search_keyframe_projection.launches", launches);
+    ctx->addStat("tracked.search_keyframe_projection.launches", C.launches);
     return FT_OK;
 }
 

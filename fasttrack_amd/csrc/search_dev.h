@@ -392,6 +392,17 @@ __device__ __forceinline__ int predict_scale(float maxDistanceRaw, float dist, f
     return nScale;
 }
 
+// key joins the ascending t[0 .. N): the N smallest candidate keys of a lane (kernels_reloc.hip, kernels_sim3.hip)
+template <int N>
+__device__ __forceinline__ void top_insert(unsigned long long t[N], unsigned long long key) {
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const unsigned long long lo = key < t[k] ? key : t[k];
+        key = key < t[k] ? t[k] : key;
+        t[k] = lo;
+    }
+}
+
 // ---- the grid of a frame (k_build_grid, k_build_grid_batch: kernels_frame.hip; k_fuse_grid: kernels_fuse.hip) ----
 // Frame::AssignFeaturesToGrid (src/Frame.cc:409-440) as one CSR per octave: workgroup (octave o, camera) counting-sorts the
 // camera's keypoints of octave o by cell cx * 48 + cy in LDS and files them behind the keypoints of the lower octaves (their

@@ -1,5 +1,5 @@
 // Host side of the projection searches, shared by the translation units of the entry-point families (search_view.cpp,
-// tracked_frame.cpp, init_search.cpp, reloc_search.cpp, tracked_batch.cpp): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
+// tracked_frame.cpp, init_search.cpp, reloc_search.cpp, triang_search.cpp, fuse_search.cpp, sim3_search.cpp, tracked_batch.cpp): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
 // (reference include/Kernels/KernelController.h:40-46) together with the acceptance loops the reference keeps in the caller
 // (src/ORBmatcher.cc:241-308, 2013-2081).  Windowing, level/box tests and every Hamming distance run on the device
 // (kernels_search*.hip, kernels_resolve.hip, kernels_frame.hip); the host only marshals arrays, drives the fixed-point passes and
@@ -536,6 +536,86 @@ inline FtDevLastPoints devLast(int M, const LastLayout &L, uint8_t *dev) {
     return D;
 }
 
+// The map points of ORBmatcher::Fuse and of SearchByProjection(pKF, Scw, ...): `who` is the entry point with its job, "name: "
+inline int checkPoints(const ft_fuse_points &P, const std::string &who) {
+    FT_REQUIRE(P.M >= 0 && P.M < (1 << 22), who + "map point count out of range");
+    FT_REQUIRE(P.M == 0 || (P.world_pos && P.normal && P.max_distance && P.min_distance && P.descriptors), who + "map point arrays are null");
+    return FT_OK;
+}
+struct PointsLayout {
+    size_t pos, nrm, maxd, mind, desc;
+};
+inline PointsLayout layoutPoints(Arena &a, size_t M) {
+    PointsLayout L;
+    L.pos = a.take(12 * M);
+    L.nrm = a.take(12 * M);
+    L.maxd = a.take(4 * M);
+    L.mind = a.take(4 * M);
+    L.desc = a.take(32 * M);
+    return L;
+}
+inline void stagePoints(const ft_fuse_points *P, const PointsLayout &L, uint8_t *pin) {
+    const size_t M = (size_t)P->M;
+    if (!M) return;
+    memcpy(pin + L.pos, P->world_pos, 12 * M);
+    memcpy(pin + L.nrm, P->normal, 12 * M);
+    memcpy(pin + L.maxd, P->max_distance, 4 * M);
+    memcpy(pin + L.mind, P->min_distance, 4 * M);
+    memcpy(pin + L.desc, P->descriptors, 32 * M);
+}
+inline FtFusePoints devPoints(int M, const PointsLayout &L, uint8_t *dev) {
+    FtFusePoints D;
+    D.M = M;
+    D.worldPos = (const float *)(dev + L.pos);
+    D.normal = (const float *)(dev + L.nrm);
+    D.maxDist = (const float *)(dev + L.maxd);
+    D.minDist = (const float *)(dev + L.mind);
+    D.desc = dev + L.desc;
+    return D;
+}
+
+// One camera of a keyframe as the one-camera frame those two searches scan: n keypoints `keys` with descriptor rows `desc`
+struct FuseSide {
+    int n, idxOffset;  // idxOffset: NLeft for the right camera
+    const ft_keypoint *keys;
+    const uint8_t *desc;
+    const float *uright;  // mvuRight where the keyframe has it (one camera), else null
+};
+inline int checkKeyframeSide(const ft_frame_view *F, bool right, const std::string &who, FuseSide &s) {
+    FT_REQUIRE(F, who + "null keyframe view");
+    FT_REQUIRE(F->N >= 0 && F->N < (1 << 24), who + "keypoint count out of range");
+    FT_REQUIRE(F->Nleft == -1 || (F->Nleft >= 0 && F->Nleft <= F->N), who + "Nleft out of range");
+    FT_REQUIRE(!right || F->Nleft != -1, who + "right on a keyframe with one camera (Nleft == -1)");
+    FT_REQUIRE(F->cam_model == 0 || F->cam_model == 1, who + "unknown camera model");
+    FT_REQUIRE(F->scale_factors && F->nlevels >= 1 && F->nlevels <= FT_MAX_LEVELS, who + "scale factors missing");
+    if (right) {
+        s.n = F->N - F->Nleft;
+        s.idxOffset = F->Nleft;
+        s.keys = F->keys_right;
+        s.desc = F->descriptors ? F->descriptors + (size_t)32 * F->Nleft : nullptr;
+        s.uright = nullptr;
+    } else {
+        s.n = F->Nleft == -1 ? F->N : F->Nleft;
+        s.idxOffset = 0;
+        s.keys = F->keys;
+        s.desc = F->descriptors;
+        s.uright = F->Nleft == -1 ? F->uright : nullptr;
+    }
+    FT_REQUIRE(s.n == 0 || (s.keys && s.desc), who + "keypoints or descriptors are null");
+    // the search reads a keypoint's octave back from four bits of its key (make_key, search_dev.h) and indexes inv_level_sigma2 with it
+    for (int i = 0; i < s.n; i++) FT_REQUIRE(s.keys[i].octave >= 0 && s.keys[i].octave < F->nlevels, who + "keypoint octave outside [0, nlevels)");
+    return FT_OK;
+}
+// the grid of that camera: cell starts per octave, then the entries as 16-byte records and 32-byte descriptors (ft_search.h)
+inline size_t sideStartBytes(int nlevels) { return (sizeof(int) * (size_t)nlevels * (FT_GRID_CELLS + 1) + 63) & ~(size_t)63; }
+inline size_t sideGridBytes(int nlevels, int n) { return sideStartBytes(nlevels) + 48 * (size_t)std::max(n, 1); }
+inline void pointSideGrid(FtDevFrame &F, uint8_t *grid, int nlevels, int n) {
+    float4 *rec = (float4 *)(grid + sideStartBytes(nlevels));
+    F.gridStart[0] = (const int *)grid;
+    F.gridRec[0] = rec;
+    F.gridDesc[0] = (const uint8_t *)(rec + std::max(n, 1));
+}
+
 // the frustum outputs as the inputs of SearchByProjection(Frame, points), where they are on the device
 inline FtDevLocalPoints localPointsOf(const FtFrustumOut &O, int M, const uint8_t *desc) {
     FtDevLocalPoints P;
@@ -634,4 +714,66 @@ struct ft_tracked_frame {
     uint8_t *d_init = nullptr, *h_init = nullptr;
     size_t initDevBytes = 0, initPinBytes = 0;
     FtEventTimer evt;
+};
+
+// The grow-only arena of a tracked frame's one-shot searches (d_init / h_init): a stream of frames settles after a few calls
+inline int ensureInitArena(ft_tracked_frame *tf, size_t devBytes, size_t pinBytes) {
+    if (devBytes <= tf->initDevBytes && pinBytes <= tf->initPinBytes) return FT_OK;
+    FT_HIP(hipStreamSynchronize(tf->ctx->stream));
+    if (tf->d_init) hipFree(tf->d_init);
+    if (tf->h_init) hipHostFree(tf->h_init);
+    tf->d_init = tf->h_init = nullptr;
+    tf->initDevBytes = tf->initPinBytes = 0;
+    FT_HIP(hipMalloc((void **)&tf->d_init, devBytes + devBytes / 4));
+    tf->initDevBytes = devBytes + devBytes / 4;
+    FT_HIP(hipHostMalloc((void **)&tf->h_init, pinBytes + pinBytes / 4, hipHostMallocDefault));
+    tf->initPinBytes = pinBytes + pinBytes / 4;
+    return FT_OK;
+}
+
+// ---- a one-shot search (initialisation, relocalisation, triangulation, Fuse, Sim3) ----
+// The event timer of a stand-alone call, destroyed with the call's scope.  (FtEventTimer itself has no destructor: extractors,
+// tracked frames and batches keep theirs for their lifetime and destroy it where they free their streams.)
+struct CallEventTimer {
+    FtEventTimer evt;
+    ~CallEventTimer() { evt.destroy(); }
+};
+// What such a call enqueues on the context's stream between its arena `dev` and the arena's pinned mirror `pin` (the context's
+// scratch, or a tracked frame's own arena with the frame's timer): blocks up, launches, one block down - and one wait.  The first
+// failure sticks: what follows is skipped, and down() waits for what was enqueued before the error leaves the entry point (the
+// next call may free the arena).  Every path of an entry point behind its first up() ends in down().
+struct CallScope {
+    ft_context *ctx;
+    hipStream_t st;
+    uint8_t *dev, *pin;
+    FtEventTimer &evt;
+    int launches = 0;
+    int rc = FT_OK;
+    void hip(hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == FT_OK) rc = ft_hip_fail(e, what, __FILE__, __LINE__);
+    }
+    void up(size_t begin, size_t end) {
+        if (rc == FT_OK) hip(hipMemcpyAsync(dev + begin, pin + begin, end - begin, hipMemcpyHostToDevice, st), "hipMemcpyAsync (block up)");
+    }
+    void zero(size_t begin, size_t end) {
+        if (rc == FT_OK) hip(hipMemsetAsync(dev + begin, 0, end - begin, st), "hipMemsetAsync");
+    }
+    // fn() enqueues one kernel; name: its kernel.* stat under ft_context_set_kernel_timing, null = not timed
+    template <typename Fn>
+    void launch(const char *name, Fn fn) {
+        if (rc != FT_OK) return;
+        const bool tm = ctx->kernelTiming && name;
+        evt.begin(tm, name, st);
+        rc = fn();
+        evt.end(tm, st);
+        launches++;
+    }
+    int down(size_t begin, size_t end) {
+        if (rc == FT_OK) hip(hipMemcpyAsync(pin + begin, dev + begin, end - begin, hipMemcpyDeviceToHost, st), "hipMemcpyAsync (block down)");
+        const hipError_t e = hipStreamSynchronize(st);
+        hip(e, "hipStreamSynchronize");
+        if (rc == FT_OK) evt.resolve(ctx);
+        else evt.recs.clear(), evt.used = 0;
+        return rc;
+    }
 };

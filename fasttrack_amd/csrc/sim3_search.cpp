@@ -10,25 +10,12 @@
 namespace {
 
 struct Sim3Layout {
-    size_t pos, nrm, maxd, mind, desc, valid;  // staged
+    PointsLayout pts;                          // staged
+    size_t valid;
     size_t matched;                            // staged and returned
     size_t nMatches, pointKeypoint, stage;     // returned
     size_t proj, top, count, walk;             // device only
 };
-
-int checkSim3Keyframe(const ft_frame_view *F, int &nLeft) {
-    const std::string w = "ft_search_keyframe_sim3: ";
-    FT_REQUIRE(F, w + "null keyframe view");
-    FT_REQUIRE(F->N >= 0 && F->N < (1 << 24), w + "keypoint count out of range");
-    FT_REQUIRE(F->Nleft == -1 || (F->Nleft >= 0 && F->Nleft <= F->N), w + "Nleft out of range");
-    FT_REQUIRE(F->cam_model == 0 || F->cam_model == 1, w + "unknown camera model");
-    FT_REQUIRE(F->scale_factors && F->nlevels >= 1 && F->nlevels <= FT_MAX_LEVELS, w + "scale factors missing");
-    nLeft = F->Nleft == -1 ? F->N : F->Nleft;
-    FT_REQUIRE(nLeft == 0 || (F->keys && F->descriptors), w + "keypoints or descriptors are null");
-    // the search reads a keypoint's octave back from four bits of its key (make_key, search_dev.h)
-    for (int i = 0; i < nLeft; i++) FT_REQUIRE(F->keys[i].octave >= 0 && F->keys[i].octave < F->nlevels, w + "keypoint octave outside [0, nlevels)");
-    return FT_OK;
-}
 
 // `bestDist<=TH_LOW*ratioHamming` (:622): an int converted to float against the float product of the int 50 and the float ratio
 int sim3Threshold(float ratio, int &thr) {
@@ -43,17 +30,14 @@ int sim3Threshold(float ratio, int &thr) {
 
 int checkSim3Job(const ft_sim3_job &j, int k, int N, FtPose &pose, int &thr) {
     const std::string w = "ft_search_keyframe_sim3: job " + std::to_string(k) + ": ";
-    const ft_fuse_points &P = j.points;
-    FT_REQUIRE(P.M >= 0 && P.M < (1 << 22), w + "map point count out of range");
-    FT_REQUIRE(P.M == 0 || (P.world_pos && P.normal && P.max_distance && P.min_distance && P.descriptors), w + "map point arrays are null");
+    int rc = checkPoints(j.points, w);
+    if (rc != FT_OK) return rc;
     FT_REQUIRE(N == 0 || j.matched, w + "null matched");
     FT_REQUIRE(j.th > 0, w + "th must be positive");
-    int rc = sim3Threshold(j.ratio_hamming, thr);
+    rc = sim3Threshold(j.ratio_hamming, thr);
     if (rc != FT_OK) return rc;
     return poseOfSe3(&j.Tcw, pose);
 }
-
-size_t sim3StartBytes(int nlevels) { return (sizeof(int) * (size_t)nlevels * (FT_GRID_CELLS + 1) + 63) & ~(size_t)63; }
 
 }  // namespace
 
@@ -63,9 +47,10 @@ int ft_search_keyframe_sim3(ft_context *ctx, const ft_frame_view *kf, int n_jobs
     FT_REQUIRE(ctx, "ft_search_keyframe_sim3: null context");
     FT_REQUIRE(n_jobs >= 0 && n_jobs < (1 << 16), "ft_search_keyframe_sim3: n_jobs out of range");
     FT_REQUIRE(n_jobs == 0 || jobs, "ft_search_keyframe_sim3: null jobs");
-    int nLeft = 0;
-    int rc = checkSim3Keyframe(kf, nLeft);
+    FuseSide side;  // the left camera
+    int rc = checkKeyframeSide(kf, false, "ft_search_keyframe_sim3: ", side);
     if (rc != FT_OK) return rc;
+    const int nLeft = side.n;
     std::vector<FtPose> poses((size_t)n_jobs);
     std::vector<int> thrs((size_t)n_jobs);
     int maxM = 0;
@@ -101,11 +86,7 @@ int ft_search_keyframe_sim3(ft_context *ctx, const ft_frame_view *kf, int n_jobs
     std::vector<Sim3Layout> L((size_t)n_jobs);
     for (int k = 0; k < n_jobs; k++) {
         const size_t m = (size_t)jobs[k].points.M;
-        L[k].pos = a.take(12 * m);
-        L[k].nrm = a.take(12 * m);
-        L[k].maxd = a.take(4 * m);
-        L[k].mind = a.take(4 * m);
-        L[k].desc = a.take(32 * m);
+        L[k].pts = layoutPoints(a, m);
         L[k].valid = jobs[k].valid ? a.take(m) : 0;
     }
     const size_t oJobs = a.take(sizeof(FtSim3Job) * (size_t)n_jobs);
@@ -126,7 +107,7 @@ int ft_search_keyframe_sim3(ft_context *ctx, const ft_frame_view *kf, int n_jobs
         L[k].count = a.take(4 * m);
         L[k].walk = a.take(4 * m);
     }
-    const size_t oGrid = a.take(sim3StartBytes(kf->nlevels) + 48 * n);
+    const size_t oGrid = a.take(sideGridBytes(kf->nlevels, nLeft));
     rc = ft_ensure_scratch(ctx, a.off, outEnd);
     if (rc != FT_OK) return rc;
     uint8_t *pin = (uint8_t *)ctx->scratchPin, *dev = (uint8_t *)ctx->scratchDev;
@@ -136,24 +117,11 @@ int ft_search_keyframe_sim3(ft_context *ctx, const ft_frame_view *kf, int n_jobs
     memset(recs, 0, sizeof(FtSim3Job) * (size_t)n_jobs);
     for (int k = 0; k < n_jobs; k++) {
         const ft_sim3_job &j = jobs[k];
-        const ft_fuse_points &P = j.points;
-        const size_t m = (size_t)P.M;
-        if (m) {
-            memcpy(pin + L[k].pos, P.world_pos, 12 * m);
-            memcpy(pin + L[k].nrm, P.normal, 12 * m);
-            memcpy(pin + L[k].maxd, P.max_distance, 4 * m);
-            memcpy(pin + L[k].mind, P.min_distance, 4 * m);
-            memcpy(pin + L[k].desc, P.descriptors, 32 * m);
-            if (j.valid) memcpy(pin + L[k].valid, j.valid, m);
-        }
+        stagePoints(&j.points, L[k].pts, pin);
+        if (j.valid && j.points.M) memcpy(pin + L[k].valid, j.valid, (size_t)j.points.M);
         memcpy(pin + L[k].matched, j.matched, 4 * n);
         FtSim3Job &R = recs[k];
-        R.M = P.M;
-        R.worldPos = (const float *)(dev + L[k].pos);
-        R.normal = (const float *)(dev + L[k].nrm);
-        R.maxDist = (const float *)(dev + L[k].maxd);
-        R.minDist = (const float *)(dev + L[k].mind);
-        R.desc = dev + L[k].desc;
+        R.P = devPoints(j.points.M, L[k].pts, dev);
         R.valid = j.valid ? dev + L[k].valid : nullptr;
         R.Tcw = poses[k];
         memcpy(R.Ow, j.Ow, sizeof R.Ow);
@@ -177,42 +145,17 @@ int ft_search_keyframe_sim3(ft_context *ctx, const ft_frame_view *kf, int n_jobs
     F.Nleft = -1;
     F.keys = (const ft_keypoint *)(dev + oKeys);
     F.desc = dev + oKfDesc;
-    uint8_t *grid = dev + oGrid;
-    float4 *rec = (float4 *)(grid + sim3StartBytes(kf->nlevels));
-    F.gridStart[0] = (const int *)grid;
-    F.gridRec[0] = rec;
-    F.gridDesc[0] = (const uint8_t *)(rec + n);
+    pointSideGrid(F, dev + oGrid, kf->nlevels, nLeft);
     const FtSim3Job *dJobs = (const FtSim3Job *)(dev + oJobs);
     hipStream_t st = ctx->stream;
-    FT_HIP(hipMemcpyAsync(dev, pin, inputEnd, hipMemcpyHostToDevice, st));  // one copy: the block is contiguous
-    const bool tm = ctx->kernelTiming;
-    FtEventTimer evt;
-    evt.begin(tm, "kernel.sim3_grid", st);
-    rc = ft_launch_sim3_grid(st, F);
-    evt.end(tm, st);
-    if (rc == FT_OK) {
-        evt.begin(tm, "kernel.sim3_candidates", st);
-        rc = ft_launch_sim3_candidates(st, F, dev, dJobs, n_jobs, maxM);
-        evt.end(tm, st);
-    }
-    if (rc == FT_OK) {
-        evt.begin(tm, "kernel.sim3_resolve", st);
-        rc = ft_launch_sim3_resolve(st, F, dev, dJobs, n_jobs);
-        evt.end(tm, st);
-    }
-    if (rc != FT_OK) {
-        hipStreamSynchronize(st);
-        evt.destroy();
-        return rc;
-    }
-    hipError_t e = hipMemcpyAsync(pin + outBegin, dev + outBegin, outEnd - outBegin, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        evt.destroy();
-        FT_HIP(e);
-    }
-    evt.resolve(ctx);
-    evt.destroy();
+    CallEventTimer own;
+    CallScope C{ctx, st, dev, pin, own.evt};
+    C.up(0, inputEnd);  // one copy: the block is contiguous
+    C.launch("kernel.sim3_grid", [&] { return ft_launch_sim3_grid(st, F); });
+    C.launch("kernel.sim3_candidates", [&] { return ft_launch_sim3_candidates(st, F, dev, dJobs, n_jobs, maxM); });
+    C.launch("kernel.sim3_resolve", [&] { return ft_launch_sim3_resolve(st, F, dev, dJobs, n_jobs); });
+    rc = C.down(outBegin, outEnd);
+    if (rc != FT_OK) return rc;
     for (int k = 0; k < n_jobs; k++) {
         ft_sim3_job &j = jobs[k];
         const size_t m = (size_t)j.points.M;
@@ -222,7 +165,7 @@ int ft_search_keyframe_sim3(ft_context *ctx, const ft_frame_view *kf, int n_jobs
         if (j.stage && m) memcpy(j.stage, pin + L[k].stage, m);
     }
     ctx->addStat("sim3.total", tAll.ms());
-    ctx->addStat("sim3.launches", 3);
+    ctx->addStat("sim3.launches", C.launches);
     return FT_OK;
 }
 

@@ -178,36 +178,18 @@ int ft_search_for_triangulation(ft_context *ctx, const ft_triang_keyframe *kf1, 
     T.coarse = coarse != 0;
     T.checkOrientation = check_orientation != 0;
     hipStream_t st = ctx->stream;
-    FT_HIP(hipMemcpyAsync(dev, pin, inputEnd, hipMemcpyHostToDevice, st));  // one copy: the block is contiguous
-    const bool tm = ctx->kernelTiming;
-    FtEventTimer evt;
-    evt.begin(tm, "kernel.triang_match", st);
-    rc = ft_launch_triang_match(st, T);
-    evt.end(tm, st);
-    if (rc == FT_OK) {
-        evt.begin(tm, "kernel.triang_finish", st);
-        rc = ft_launch_triang_finish(st, T);
-        evt.end(tm, st);
-    }
-    if (rc != FT_OK) {
-        hipStreamSynchronize(st);
-        evt.destroy();
-        return rc;
-    }
-    const size_t downEnd = best_dist ? a.off : outEnd;
-    hipError_t e = hipMemcpyAsync(pin + oMatches, dev + oMatches, downEnd - oMatches, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        evt.destroy();
-        FT_HIP(e);
-    }
-    evt.resolve(ctx);
-    evt.destroy();
+    CallEventTimer own;
+    CallScope C{ctx, st, dev, pin, own.evt};
+    C.up(0, inputEnd);  // one copy: the block is contiguous
+    C.launch("kernel.triang_match", [&] { return ft_launch_triang_match(st, T); });
+    C.launch("kernel.triang_finish", [&] { return ft_launch_triang_finish(st, T); });
+    rc = C.down(oMatches, best_dist ? a.off : outEnd);
+    if (rc != FT_OK) return rc;
     memcpy(matches12, pin + oMatches, rows);
     memcpy(n_matches, pin + oCount, 4 * (size_t)n_neighbours);
     if (best_dist) memcpy(best_dist, pin + oBest, rows);
     ctx->addStat("search_for_triangulation.total", tAll.ms());
-    ctx->addStat("search_for_triangulation.launches", 2);
+    ctx->addStat("search_for_triangulation.launches", C.launches);
     return FT_OK;
 }
 

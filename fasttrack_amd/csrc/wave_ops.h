@@ -86,6 +86,15 @@ __device__ __forceinline__ unsigned row_min_u32(unsigned v) {
     return v;
 }
 
+// sum over the row, in every lane of it
+__device__ __forceinline__ int row_sum_i32(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
+    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);  // row_half_mirror
+    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);  // row_mirror
+    return v;
+}
+
 // maximum over the row of 16 lanes, in every lane of it
 __device__ __forceinline__ int row_max_i32(int v) {
     v = max(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));
@@ -93,6 +102,12 @@ __device__ __forceinline__ int row_max_i32(int v) {
     v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));
     v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));
     return v;
+}
+
+// row i of the descriptors `desc` (32 bytes each) as 4 x uint64
+__device__ __forceinline__ void load_desc256(const uint8_t *desc, int i, unsigned long long q[4]) {
+    const unsigned long long *d = (const unsigned long long *)(desc + (size_t)i * 32);
+    q[0] = d[0]; q[1] = d[1]; q[2] = d[2]; q[3] = d[3];
 }
 
 // ORBmatcher::DescriptorDistance (reference src/ORBmatcher.cc:2256-2272) of two 256-bit descriptors as 4 x uint64
