@@ -234,7 +234,7 @@ struct ft_extractor {
     ft_keypoint *d_stKeys = nullptr;  // [2 * maxKp] left then right
     uint8_t *d_stDesc = nullptr;      // [2 * maxKp * 32]
     float *d_stOut = nullptr;         // [2 * maxKp] uright then depth
-    int *d_stInt = nullptr;           // [2 * stCap + 4] sad, hamming idx, then nL nR nMatches, then the row starts
+    int *d_stInt = nullptr;           // [2 * stCap + 4] sad, hamming idx, then nL nR nMatches, then the row starts, then [stCap] left order
     FtSortedR *d_stSorted = nullptr;  // [stCap] right keypoints in row-bucket order
     int stCap = 0;
     FtEventTimer evt;
@@ -260,6 +260,7 @@ struct ft_stereo_frontend {
     bool pairedCapable = false, lastPaired = false;
     FtSortedR *d_sorted = nullptr;  // right keypoints bucketed by row (k_stereo_rowsort)
     int *d_rowStart = nullptr;
+    int *d_leftOrder = nullptr;     // left keypoint indices in row order (k_stereo_rowsort)
     hipEvent_t evR = nullptr;
     // Latency mode: a small batch with a fixed call shape (same sizes, same result arrays, same kind of input) is
     // captured once as a HIP graph - ~45 enqueue calls on seven streams become one launch.  graphKey holds everything

@@ -57,7 +57,7 @@ int ft_stereo_match(ft_extractor *exL, ft_extractor *exR, int slot, const ft_key
         FT_HIP(hipMalloc((void **)&exL->d_stKeys, sizeof(ft_keypoint) * 2 * need));
         FT_HIP(hipMalloc((void **)&exL->d_stDesc, (size_t)64 * need));
         FT_HIP(hipMalloc((void **)&exL->d_stOut, sizeof(float) * 2 * need));
-        FT_HIP(hipMalloc((void **)&exL->d_stInt, sizeof(int) * (2 * (size_t)need + 8 + exL->height + 2)));
+        FT_HIP(hipMalloc((void **)&exL->d_stInt, sizeof(int) * (3 * (size_t)need + 8 + exL->height + 2)));
         FT_HIP(hipMalloc((void **)&exL->d_stSorted, sizeof(FtSortedR) * (size_t)need));
         exL->stCap = need;
     }
@@ -94,6 +94,7 @@ int ft_stereo_match(ft_extractor *exL, ft_extractor *exR, int slot, const ft_key
     a.sorted = exL->d_stSorted;
     a.rowStart = exL->d_stInt + 2 * C + 4;
     a.rowStride = exL->height + 2;
+    a.leftOrder = a.rowStart + a.rowStride;
     a.alignedLoads = exL->l0Aligned && exR->l0Aligned;
     rc = ft_launch_stereo_rowsort(st, g, 1, a);
     if (rc != FT_OK) return rc;
@@ -142,6 +143,7 @@ int ft_stereo_frontend_create(ft_context *ctx, int nfeatures, float scale_factor
     if (e == hipSuccess) e = hipMalloc((void **)&fe->d_nMatches, sizeof(int) * max_batch);
     if (e == hipSuccess) e = hipMalloc((void **)&fe->d_sorted, sizeof(FtSortedR) * n);
     if (e == hipSuccess) e = hipMalloc((void **)&fe->d_rowStart, sizeof(int) * (size_t)max_batch * (image_height + 2));
+    if (e == hipSuccess) e = hipMalloc((void **)&fe->d_leftOrder, sizeof(int) * n);
     if (e == hipSuccess) e = hipHostMalloc((void **)&fe->h_uright, sizeof(float) * n, hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc((void **)&fe->h_depth, sizeof(float) * n, hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc((void **)&fe->h_nMatches, sizeof(int) * max_batch, hipHostMallocDefault);
@@ -168,6 +170,7 @@ int ft_stereo_frontend_destroy(ft_stereo_frontend *fe) {
     hipFree(fe->d_nMatches);
     hipFree(fe->d_sorted);
     hipFree(fe->d_rowStart);
+    hipFree(fe->d_leftOrder);
     hipHostFree(fe->h_uright);
     hipHostFree(fe->h_depth);
     hipHostFree(fe->h_nMatches);
@@ -238,6 +241,7 @@ static int frontendMatchAndDeliver(ft_stereo_frontend *fe, int s, int b0, int nb
     a.rowStride = L->height + 2;
     a.rowStart = fe->d_rowStart + (size_t)b0 * a.rowStride;
     a.sorted = fe->d_sorted + o;
+    a.leftOrder = fe->d_leftOrder + o;
     a.alignedLoads = L->l0Aligned && R->l0Aligned;
     L->evt.begin(tm, "kernel.stereo_rowsort", st);
     rc = ft_launch_stereo_rowsort(st, g, nb, a);
@@ -321,6 +325,7 @@ static int frontendEnqueue(ft_stereo_frontend *fe, const uint8_t *const *imagesL
         a.rowStride = L->height + 2;
         a.rowStart = fe->d_rowStart;
         a.sorted = fe->d_sorted;
+        a.leftOrder = fe->d_leftOrder;
         a.alignedLoads = L->l0Aligned;
         rc = ft_launch_stereo_rowsort(st, g, B, a);
         if (rc == FT_OK)
