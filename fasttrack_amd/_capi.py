@@ -277,6 +277,7 @@ def lib() -> C.CDLL:
                                    C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]
     L.ft_octree_distribute.argtypes = [vp, i, i, i, i, i, i, vp, i, ip]
     L.ft_level_geometry.argtypes = [i, i, i, f, i, vp, vp, vp, vp, vp, vp, vp]
+    L.ft_pyramid_band_plan.argtypes = [i, i, f, i, i, vp, vp]
     _lib = L
     return L
 

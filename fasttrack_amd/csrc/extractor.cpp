@@ -139,6 +139,43 @@ int buildGeometry(ft_extractor *ex, std::vector<FtTap> &taps) {
     return FT_OK;
 }
 
+}  // namespace
+
+void ft_pyr_bands_of(const FtGeom &g, int K, int *first, int *end) {
+    for (int k = 0; k < K; k++) first[k] = end[k] = 0;  // (level 0)
+    std::vector<FtTap> yt;
+    for (int k = 0; k < K; k++) {
+        int lo = 0, hi = 0;  // the band's range one level up
+        for (int l = g.nlevels - 1; l >= 1; l--) {
+            const int H = g.lv[l].h;
+            int a = (int)((long long)k * H / K), b = (int)((long long)(k + 1) * H / K);
+            if (hi > lo) {  // the rows of level l that rows [lo, hi) of level l + 1 are made of
+                int s0, s1;
+                if (g.lv[l + 1].area2x) {
+                    s0 = 2 * lo;
+                    s1 = 2 * (hi - 1) + 2;
+                } else {
+                    yt.resize(g.lv[l + 1].h);
+                    buildTaps(H, g.lv[l + 1].h, false, yt.data());
+                    s0 = std::min(std::max((int)yt[lo].s, 0), H - 1);
+                    s1 = std::min(std::max((int)yt[hi - 1].s + 1, 0), H - 1) + 1;
+                }
+                if (b > a) {
+                    a = std::min(a, s0);
+                    b = std::max(b, s1);
+                } else {
+                    a = s0;
+                    b = s1;
+                }
+            }
+            first[l * K + k] = lo = a;
+            end[l * K + k] = hi = b;
+        }
+    }
+}
+
+namespace {
+
 template <typename T>
 int devAlloc(T **p, size_t n) {
     FT_HIP(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
@@ -406,8 +443,12 @@ int ft_extract_launch_a(ft_extractor *ex, int b0, int nb, hipEvent_t done) {
     uint8_t *pyr = ex->d_pyr + (size_t)b0 * g.pyrPerSlot;
     int *cellCount = ex->d_cellCount + (size_t)b0 * g.totalCells;
     uint32_t *stage = ex->d_stage + (size_t)b0 * g.stagePerSlot;
+    // a captured latency batch keeps the per-level launches: its few images would leave the one-launch form on a few CUs
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    FT_HIP(hipStreamIsCapturing(ex->stream, &cap));
     ex->evt.begin(tm, "kernel.pyr_down(all levels)", ex->stream);
-    int rc = ft_launch_pyramid(ex->stream, g, nb, l0, ex->l0pitch, pyr, ex->d_taps, al, ex->tune.pyr_rows);
+    int rc = ft_launch_pyramid(ex->stream, g, nb, l0, ex->l0pitch, pyr, ex->d_taps, al, ex->tune.pyr_rows,
+                               cap == hipStreamCaptureStatusNone ? &ex->pyrBands : nullptr);
     ex->evt.end(tm, ex->stream);
     if (rc != FT_OK) return rc;
     ex->evt.begin(tm, "kernel.fast_cells", ex->stream);
@@ -788,6 +829,13 @@ int ft_extractor_create(ft_context *ctx, int nfeatures, float scale_factor, int 
     }
     const FtGeom &g = ex->geom;
     const size_t B = max_batch;
+    {  // the band plan of the one-launch pyramid
+        int first[FT_MAX_LEVELS * PC_BANDS], end[FT_MAX_LEVELS * PC_BANDS];
+        ft_pyr_bands_of(g, PC_BANDS, first, end);
+        ex->pyrBands.K = PC_BANDS;
+        for (int l = 1; l < g.nlevels; l++)
+            for (int k = 0; k < PC_BANDS; k++) ex->pyrBands.rows[l][k] = (unsigned)first[l * PC_BANDS + k] | ((unsigned)end[l * PC_BANDS + k] << 16);
+    }
 #define FT_TRY(x)            \
     do {                     \
         rc = (x);            \
@@ -1013,6 +1061,21 @@ int ft_level_geometry(int width, int height, int nfeatures, float scale_factor, 
         if (w_cell) w_cell[l] = v.wCell;
         if (h_cell) h_cell[l] = v.hCell;
     }
+    return FT_OK;
+}
+
+int ft_pyramid_band_plan(int width, int height, float scale_factor, int nlevels, int bands, int *first_row, int *end_row) {
+    FT_REQUIRE(nlevels >= 1 && nlevels <= FT_MAX_LEVELS && scale_factor > 1.0f && bands >= 1 && first_row && end_row, "bad parameters");
+    ft_extractor ex;
+    ex.nfeatures = 1000;
+    ex.scaleFactor = scale_factor;
+    ex.nlevels = nlevels;
+    ex.width = width;
+    ex.height = height;
+    std::vector<FtTap> taps;
+    int rc = buildGeometry(&ex, taps);
+    if (rc != FT_OK) return rc;
+    ft_pyr_bands_of(ex.geom, bands, first_row, end_row);
     return FT_OK;
 }
 

@@ -45,7 +45,7 @@
     X(oct_hist, "FT_OCT_HIST", 1, 0, 1, "histogram tier of the device octree for levels above 4096 candidates")              \
     X(oct_hist_first, "FT_OCT_HIST_FIRST", 1, 0, 2, "histogram formulation for every level: 0 never, 1 latency-mode launches, 2 always") \
     X(oct_big, "FT_OCT_BIG", 1, 0, 1, "sorted big tier of the device octree (up to 16384 keys per level)")                   \
-    X(pyr_rows, "FT_PYR_ROWS", 1, 0, 1, "pyramid of launches of 8+ images: 1 = row-streaming kernel (k_pyr_rows), 0 = tile kernel (k_pyr_down)") \
+    X(pyr_rows, "FT_PYR_ROWS", 2, 0, 2, "pyramid of launches of 8+ images: 2 = all levels in one launch, a workgroup per band of an image (k_pyr_cascade), 1 = row-streaming kernel, a launch per level (k_pyr_rows), 0 = tile kernel (k_pyr_down)") \
     X(upload_kernel, "FT_UPLOAD_KERNEL", 1, 0, 1, "latency mode: frames go up through k_upload instead of DMA copies")       \
     X(graph, "FT_GRAPH", 1, 0, 1, "latency mode: batches of <= 8 frames are captured and replayed as HIP graphs")            \
     X(paired, "FT_PAIRED", 1, 0, 1, "latency-mode stereo front ends run both cameras through one set of launches")           \
@@ -162,6 +162,7 @@ struct ft_extractor {
     std::vector<int> levelMax;  // per-level bound of octree results
     std::vector<int> levelOff;  // prefix sums of levelMax
     FtGeom geom{};
+    FtPyrBands pyrBands{};  // band plan of the one-launch pyramid (ft_pyr_bands_of)
     hipStream_t stream = nullptr;   // stage A (pyramid, FAST, compaction)
     hipStream_t streamB = nullptr;  // stage B (orientation + descriptors), matching, result copies
     hipEvent_t evA[FT_PIPE_MAX] = {}, evB[FT_PIPE_MAX] = {};

@@ -184,9 +184,29 @@ const char *ft_debug_env(const char *name);  // FT_DEBUG_* aids only (context.cp
     } while (0)
 
 // ---- kernel launchers (kernels_extract.hip) -------------------------------------------------
-// l0: device array [batch] of level-0 pointers; pyr: base of the slot pyramids
+// The one-launch pyramid (k_pyr_cascade): an image is cut into K horizontal bands, a workgroup of PC_WAVES waves owns one band
+// through all levels.  rows[level][band] = first | end << 16 of the band's row range at that level (levels 1 .. n - 1).
+// Two bands of sixteen waves: measured on the default bench against 1 x 8 / 1 x 16 / 2 x 4 / 2 x 8 / 2 x 12 / 3 x 8 / 4 x 4 / 4 x 8 /
+// 8 x 4 (EXPERIMENTS 22).
+#ifndef PC_BANDS
+#define PC_BANDS 2
+#endif
+#ifndef PC_WAVES
+#define PC_WAVES 16
+#endif
+#define FT_PYR_BANDS_MAX 8
+struct FtPyrBands {
+    int K;
+    unsigned rows[FT_MAX_LEVELS][FT_PYR_BANDS_MAX];
+};
+// The plan (host, extractor.cpp): band k owns rows [k H_l / K, (k + 1) H_l / K) of level l; going down from the top level its
+// range at level l is the hull of its own rows and of the source rows its range at level l + 1 reads (the y taps of the
+// resize, clamped; 2 dy, 2 dy + 1 on an exact-2x level).  first / end: [level * K + band], level 0 unused.
+void ft_pyr_bands_of(const FtGeom &g, int K, int *first, int *end);
+// l0: device array [batch] of level-0 pointers; pyr: base of the slot pyramids; rowsKernel: option pyr_rows; bands: the plan
+// of the one-launch form (rowsKernel = 2), null = none
 int ft_launch_pyramid(hipStream_t st, const FtGeom &g, int batch, const uint8_t *const *l0, int l0pitch,
-                      uint8_t *pyr, const FtTap *taps, int alignedLoads, int rowsKernel);
+                      uint8_t *pyr, const FtTap *taps, int alignedLoads, int rowsKernel, const FtPyrBands *bands);
 // the cells a k_fast_cells launch covers: up to two runs of consecutive cells of the per-image cell table
 struct FtCellRanges {
     int lo0, n0, lo1, n1;

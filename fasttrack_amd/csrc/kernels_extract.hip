@@ -267,20 +267,15 @@ __device__ __forceinline__ unsigned umulhi_su(unsigned bShifted16, unsigned a) {
     asm("v_mul_hi_u32 %0, %1, %2" : "=v"(r) : "s"(bShifted16), "v"(a));
     return r;
 }
-template <bool AREA>
-__global__ __launch_bounds__(64) void k_pyr_rows(FtGeom g, int level, const uint8_t *const *l0, int l0pitch, uint8_t *pyr,
-                                                 const FtTap *taps, FtSlotGrid sg, int stripsX, unsigned sxMagic,
-                                                 int readableEnd) {
-    const int lane = threadIdx.x;
-    int slot, tile;
-    if (!ft_slot_block(sg, slot, tile)) return;
-    const int ty = div_by(tile, sxMagic), tx = tile - ty * stripsX;
+// one strip: columns [tx * PR_COLS, + PR_COLS) x up to PR_RB rows from j0, short of row rowEnd (BAND) or of the level's height,
+// of `level` of image `slot`, from the level below at S with row pitch spitch (all wave-uniform)
+template <bool AREA, bool BAND>
+__device__ __forceinline__ void pyr_rows_strip(const FtGeom &g, int level, int slot, int tx, int j0, int rowEnd, int lane,
+                                               const uint8_t *S, int spitch, uint8_t *pyr, const FtTap *taps, int readableEnd) {
     const FtLevelGeom &D = g.lv[level];
-    int spitch;
-    const uint8_t *S = level_ptr(g, level - 1, slot, l0, l0pitch, pyr, spitch);
     const int sw = g.lv[level - 1].w, sh = g.lv[level - 1].h;
     const int dx = tx * PR_COLS + 2 * lane;  // first of this lane's two output columns
-    const int j0 = ty * PR_RB, nrows = min(PR_RB, D.h - j0);
+    const int nrows = min(PR_RB, (BAND ? rowEnd : D.h) - j0);
     // row taps: lane r holds the two source rows (clamped to the level, packed sy0 | sy1 << 16) and the two weights
     // (b0 | b1 << 16) of output row j0 + r - unpacked and clamped once here, by the vector unit for all rows at a time;
     // the loop below reads a row's pair with two v_readlane and four scalar instructions
@@ -414,6 +409,59 @@ __global__ __launch_bounds__(64) void k_pyr_rows(FtGeom g, int level, const uint
     };
     if (tx * PR_COLS + PR_COLS <= D.w) run(std::false_type{});  // wave-uniform
     else run(std::true_type{});
+}
+
+template <bool AREA>
+__global__ __launch_bounds__(64) void k_pyr_rows(FtGeom g, int level, const uint8_t *const *l0, int l0pitch, uint8_t *pyr,
+                                                 const FtTap *taps, FtSlotGrid sg, int stripsX, unsigned sxMagic,
+                                                 int readableEnd) {
+    const int lane = threadIdx.x;
+    int slot, tile;
+    if (!ft_slot_block(sg, slot, tile)) return;
+    const int ty = div_by(tile, sxMagic), tx = tile - ty * stripsX;
+    int spitch;
+    const uint8_t *S = level_ptr(g, level - 1, slot, l0, l0pitch, pyr, spitch);
+    pyr_rows_strip<AREA, false>(g, level, slot, tx, ty * PR_RB, 0, lane, S, spitch, pyr, taps, readableEnd);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pyramid, all levels in ONE launch: an image is cut into K horizontal bands (FtPyrBands, planned on the host by
+// ft_pyr_bands_of) and a workgroup of PC_WAVES waves walks one band of one image through the levels 1 .. n - 1.  At every
+// level the band's row range is the hull of the rows it owns and of the source rows its range one level up reads, so a
+// workgroup only ever reads rows that it wrote itself (rows in the overlap of two bands are computed by both, with the
+// same bytes): no dependency between workgroups, no waiting on memory.  Inside the workgroup a level is handed to the next
+// by a workgroup barrier between a release and an acquire fence; the waves of a workgroup share one CU's vector L1 (the
+// Makefile refuses -mtgsplit), so what a wave stored is what the others load.  Pyramid pixels stay on vector loads and
+// stores (pyr_rows_strip: gload / gstore), never on scalar loads: the scalar cache is not coherent with them.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * PC_WAVES) void k_pyr_cascade(FtGeom g, const uint8_t *const *l0, int l0pitch, uint8_t *pyr,
+                                                              const FtTap *taps, FtSlotGrid sg, FtPyrBands pb,
+                                                              int l0ReadableEnd) {
+    const int lane = threadIdx.x & 63, wave = wave_index();
+    int slot, band;
+    if (!ft_slot_block(sg, slot, band)) return;  // (the whole workgroup)
+    const uint8_t *const frame = l0[slot];  // read before the first store: a scalar load
+    for (int level = 1; level < g.nlevels; level++) {
+        const unsigned rr = pb.rows[level][band];
+        const int r0 = (int)(rr & 0xffffu), r1 = (int)(rr >> 16);  // an empty range (r0 == r1) runs no strip
+        const int stripsX = (g.lv[level].w + PR_COLS - 1) / PR_COLS;
+        const unsigned sxMagic = div_magic_small((unsigned)stripsX);
+        const int n = stripsX * ((r1 - r0 + PR_RB - 1) / PR_RB);
+        const int readableEnd = level == 1 ? l0ReadableEnd : g.lv[level - 1].pitch;
+        const int spitch = level == 1 ? l0pitch : g.lv[level - 1].pitch;
+        const uint8_t *S = level == 1 ? frame : pyr + (size_t)slot * g.pyrPerSlot + g.lv[level - 1].off;
+        for (int s = wave; s < n; s += PC_WAVES) {
+            const int ty = div_by(s, sxMagic), tx = s - ty * stripsX;
+            const int j0 = r0 + ty * PR_RB;
+            if (g.lv[level].area2x) pyr_rows_strip<true, true>(g, level, slot, tx, j0, r1, lane, S, spitch, pyr, taps, readableEnd);
+            else pyr_rows_strip<false, true>(g, level, slot, tx, j0, r1, lane, S, spitch, pyr, taps, readableEnd);
+        }
+        if (level + 1 < g.nlevels) {  // every wave of the workgroup passes here, whatever its band holds at this level
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __syncthreads();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1676,8 +1724,20 @@ static bool pyr_rows_fits(const FtGeom &g, int level) {
 }
 
 int ft_launch_pyramid(hipStream_t st, const FtGeom &g, int batch, const uint8_t *const *l0, int l0pitch,
-                      uint8_t *pyr, const FtTap *taps, int alignedLoads, int rowsKernel) {
+                      uint8_t *pyr, const FtTap *taps, int alignedLoads, int rowsKernel, const FtPyrBands *bands) {
     const bool rowsOn = rowsKernel != 0;
+    // wide launches whose every level the row-streaming strip can produce: all levels in one launch (k_pyr_cascade)
+    bool cascade = rowsKernel == 2 && batch >= 8 && alignedLoads && bands && bands->K >= 1 && g.nlevels >= 2;
+    for (int level = 1; cascade && level < g.nlevels; level++) cascade = pyr_rows_fits(g, level);
+    if (cascade) {
+        dim3 grid, block(64 * PC_WAVES, 1, 1);
+        const FtSlotGrid sg = ft_slot_grid(bands->K, batch, grid);
+        const int readableEnd = std::min((g.lv[0].w + 3) & ~3, l0pitch);  // of a row of the caller's frame (see below)
+        for (int rep = ft_debug_repeat("pyr"); rep > 0; rep--)
+            hipLaunchKernelGGL(k_pyr_cascade, grid, block, 0, st, g, l0, l0pitch, pyr, taps, sg, *bands, readableEnd);
+        FT_HIP(hipGetLastError());
+        return FT_OK;
+    }
     for (int rep = ft_debug_repeat("pyr"); rep > 0; rep--)
     for (int level = 1; level < g.nlevels; level++) {
         const FtLevelGeom &D = g.lv[level], &P = g.lv[level - 1];

@@ -86,7 +86,9 @@ FT_API int ft_context_set_lane_map(ft_context *ctx, const int *map, int n);
  *   oct_hist             1        0 .. 1   histogram tier of the device octree for levels above 4096 candidates
  *   oct_hist_first       1        0 .. 2   histogram formulation for every level: 0 never, 1 latency-mode launches, 2 always
  *   oct_big              1        0 .. 1   sorted big tier of the device octree (up to 16384 keys per level)
- *   pyr_rows             1        0 .. 1   pyramid of launches of 8+ images: 1 = row-streaming kernel, 0 = tile kernel
+ *   pyr_rows             2        0 .. 2   pyramid of launches of 8+ images: 2 = all levels in one launch, a workgroup per band
+ *                                          of an image (a per-level loop of the row-streaming kernel where a level does not fit
+ *                                          it), 1 = row-streaming kernel, a launch per level, 0 = tile kernel
  *   upload_kernel        1        0 .. 1   latency mode: frames go up through one kernel instead of DMA copies
  *   graph                1        0 .. 1   latency mode: batches of <= 8 frames are captured and replayed as HIP graphs
  *   paired               1        0 .. 1   latency-mode stereo front ends run both cameras through one set of launches
@@ -215,6 +217,11 @@ FT_API int ft_octree_distribute(const int *xys, int n, int minX, int maxX, int m
                                 int capacity, int *n_out);
 FT_API int ft_level_geometry(int width, int height, int nfeatures, float scale_factor, int nlevels, int *level_w,
                              int *level_h, int *quota, int *n_cols, int *n_rows, int *w_cell, int *h_cell);
+/* The plan of the one-launch pyramid (pyr_rows = 2), host only: an image is cut into `bands` horizontal bands, band k owns rows
+ * [k H / bands, (k + 1) H / bands) of every level (H = the level's height); its row range at a level is the hull of those and of
+ * the source rows its range one level up is resized from, so a band reads only rows it wrote.  first_row / end_row:
+ * [level * bands + band] for levels 1 .. nlevels - 1 (level 0 entries are zero); first == end: the band has nothing at that level. */
+FT_API int ft_pyramid_band_plan(int width, int height, float scale_factor, int nlevels, int bands, int *first_row, int *end_row);
 
 /* ------------------------------------------------------------------------------------------------
  * Stereo matching, rectified pinhole pair.

@@ -9,7 +9,7 @@ import sqlite3
 import sys
 from collections import defaultdict
 
-WIDE = ("k_fast_cells", "k_orient_desc", "k_pyr_rows", "k_stereo_match", "k_octree", "k_compact")
+WIDE = ("k_fast_cells", "k_orient_desc", "k_pyr_rows", "k_pyr_cascade", "k_stereo_match", "k_octree", "k_compact")
 
 
 def short(n):

@@ -29,7 +29,7 @@ def run(repeat):
 
 
 base = run("")
-names = {"fast": "k_fast_cells", "pyr": "k_pyr_rows (7 launches)", "octree": "k_octree", "orient": "k_orient_desc",
+names = {"fast": "k_fast_cells", "pyr": "k_pyr_cascade (pyr_rows = 1: k_pyr_rows, 7 launches)", "octree": "k_octree", "orient": "k_orient_desc",
          "stereo": "k_stereo_match", "compact": "k_compact", "rowsort": "k_stereo_rowsort", "median": "k_stereo_median"}
 doubled, marg = {}, {}
 for key, name in names.items():

@@ -35,6 +35,7 @@ KERNELS = [
     ("kernels_extract.hip", "k_orient_descILi2EE", "k_orient_desc<2>"),
     ("kernels_extract.hip", "k_pyr_rowsILb0EE", "k_pyr_rows<false>"),
     ("kernels_extract.hip", "k_pyr_rowsILb1EE", "k_pyr_rows<true>"),
+    ("kernels_extract.hip", "13k_pyr_cascadeE", "k_pyr_cascade"),
     ("kernels_extract.hip", "9k_compactE", "k_compact"),
     ("kernels_octree.hip", "8k_octreeE", "k_octree"),
     ("kernels_match.hip", "14k_stereo_matchE", "k_stereo_match"),
