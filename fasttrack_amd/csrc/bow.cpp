@@ -13,14 +13,6 @@
 
 #include "ft_host.h"
 
-#define FT_REQUIRE(cond, msg)               \
-    do {                                    \
-        if (!(cond)) {                      \
-            ft_set_error(msg);              \
-            return FT_ERR_INVALID;          \
-        }                                   \
-    } while (0)
-
 struct ft_vocabulary {
     ft_context *ctx = nullptr;
     int k = 0, L = 0, scoring = 0, weighting = 0, nNodes = 0, nWords = 0;

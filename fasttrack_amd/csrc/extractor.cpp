@@ -4,6 +4,7 @@
 // touched by the HIP kernels in kernels_extract.hip.  Compiled with -ffp-contract=off.
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -15,14 +16,6 @@ namespace {
 
 inline int cvRoundF(float v) { return (int)lrintf(v); }
 inline short satShort(int v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
-
-#define FT_REQUIRE(cond, msg)                      \
-    do {                                           \
-        if (!(cond)) {                             \
-            ft_set_error(std::string(msg));        \
-            return FT_ERR_INVALID;                 \
-        }                                          \
-    } while (0)
 
 // cv::resize INTER_LINEAR coefficient tables: index + two 11-bit weights per output
 // column / row.  scale = 1 / (dsize / ssize) in double, fx in float, weights via cvRound.
@@ -176,93 +169,29 @@ void ft_pyr_bands_of(const FtGeom &g, int K, int *first, int *end) {
 
 namespace {
 
-template <typename T>
-int devAlloc(T **p, size_t n) {
-    FT_HIP(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    return FT_OK;
-}
-template <typename T>
-int pinAlloc(T **p, size_t n, unsigned flags = hipHostMallocDefault) {
-    FT_HIP(hipHostMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T), flags));
-    return FT_OK;
-}
-
+// waits for the extractor's streams, hands them back and releases what the extractor owns
 void freeAll(ft_extractor *ex) {
     hipSetDevice(ex->ctx->device);
-    if (ex->stream) hipStreamSynchronize(ex->stream);
-    if (ex->streamB) hipStreamSynchronize(ex->streamB);
-    for (int i = 0; i < FT_OCT_STREAMS; i++)
-        if (ex->streamO[i]) hipStreamSynchronize(ex->streamO[i]);
-    if (ex->octLayout.prof) {  // FT_OCT_PROFILE=1: phase times of the octree kernel (slot 0 of every launch)
+    hipStream_t all[FT_LANE_STREAMS] = {ex->stream, ex->streamB};
+    for (int i = 0; i < FT_OCT_STREAMS; i++) all[2 + i] = ex->streamO[i];
+    for (hipStream_t st : all)
+        if (st) hipStreamSynchronize(st);
+    if (ex->octLayout.prof) {  // FT_DEBUG_OCT_PROFILE=1: phase times of the octree kernel (slot 0 of every launch)
         unsigned long long h[FT_MAX_LEVELS * 8];
         if (hipMemcpy(h, ex->octLayout.prof, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
             for (int l = 0; l < ex->nlevels; l++)
                 fprintf(stderr, "[oct profile] level %d: codes %.1f us  sort %.1f us  rounds %.1f us (std::sort replay %.1f us, %llu elems in %llu sorts)  pick %.1f us\n",
                         l, h[l * 8] * 0.01, h[l * 8 + 1] * 0.01, h[l * 8 + 2] * 0.01, h[l * 8 + 4] * 0.01, h[l * 8 + 5], h[l * 8 + 6], h[l * 8 + 3] * 0.01);
-        hipFree(ex->octLayout.prof);
-        ex->octLayout.prof = nullptr;
     }
     ex->evt.destroy();
-    for (int i = 0; i < FT_PIPE_MAX; i++) {
-        if (ex->evA[i]) hipEventDestroy(ex->evA[i]);
-        if (ex->evB[i]) hipEventDestroy(ex->evB[i]);
-        if (ex->evO[i]) hipEventDestroy(ex->evO[i]);
-    }
-    if (ex->evJoin) hipEventDestroy(ex->evJoin);
-    if (ex->evUp) hipEventDestroy(ex->evUp);
     if (ex->graphExec) hipGraphExecDestroy(ex->graphExec);
-    for (int i = 0; i < FT_OCT_STREAMS; i++)
-        if (ex->streamO[i]) {
-            hipStreamSynchronize(ex->streamO[i]);
-            if (ex->ownStreams) hipStreamDestroy(ex->streamO[i]);
-        }
-    if (ex->streamB) {
-        hipStreamSynchronize(ex->streamB);
-        if (ex->ownStreams) hipStreamDestroy(ex->streamB);
-    }
-    hipFree(ex->d_pyr);
-    if (ex->h_stage) hipHostFree(ex->h_stage);
-    if (ex->h_srcTab) hipHostFree(ex->h_srcTab);
-    hipFree(ex->d_taps);
-    hipFree(ex->d_cellTab);
-    hipFree(ex->d_cellCount);
-    hipFree(ex->d_stage);
-    hipFree((void *)ex->d_l0);
-    hipFree(ex->d_sel);
-    hipFree(ex->d_nSel);
-    hipFree(ex->d_selCount);
-    hipFree(ex->d_overflow);
-    hipFree(ex->d_ovSlot);
-    hipFree(ex->d_bigCount);
-    hipHostFree(ex->h_bigStat);
-    hipHostFree(ex->h_histStat);
-    hipFree(ex->d_bigList);
-    hipFree(ex->d_sortList);
-    hipFree(ex->d_octLow);
-    if (ex->h_repCand) hipHostFree(ex->h_repCand);
-    hipFree(ex->d_candDev);
-    hipFree(ex->d_candCountDev);
-    hipHostFree(ex->h_selCount);
-    hipHostFree(ex->h_overflow);
-    hipFree(ex->d_keys);
-    hipFree(ex->d_desc);
-    hipFree(ex->d_stKeys);
-    hipFree(ex->d_stDesc);
-    hipFree(ex->d_stOut);
-    hipFree(ex->d_stInt);
-    hipFree(ex->d_stSorted);
-    hipHostFree((void *)ex->h_l0);
-    hipHostFree(ex->h_cand);
-    hipHostFree(ex->h_candCount);
-    hipHostFree(ex->h_sel);
-    hipHostFree(ex->h_nSel);
-    hipHostFree(ex->h_nMono);
-    hipHostFree(ex->h_keys);
-    hipHostFree(ex->h_desc);
-    if (ex->stream) {
-        hipStreamSynchronize(ex->stream);
-        if (ex->ownStreams) hipStreamDestroy(ex->stream);
-    }
+    for (hipStream_t st : all)
+        if (st && ex->ownStreams) hipStreamDestroy(st);
+    ex->own.release();
+}
+void destroyExtractor(ft_extractor *ex) {
+    freeAll(ex);
+    delete ex;
 }
 
 }  // namespace
@@ -316,7 +245,6 @@ int ft_extract_prepare(ft_extractor *ex, const uint8_t *const *images, int batch
             ex->h_l0[b] = ex->d_pyr + (size_t)b * g.pyrPerSlot + g.lv[0].off;
         }
         ft_extract_restage(ex, images, batch, width, height, stride);
-        ex->l0External = false;
         ex->l0Aligned = true;
         ex->l0pitch = g.lv[0].pitch;
         ex->lastBatch = batch;
@@ -378,14 +306,8 @@ int ft_extract_prepare(ft_extractor *ex, const uint8_t *const *images, int batch
         FT_HIP(hipEventRecord(ex->evUp, us));
         FT_HIP(hipStreamWaitEvent(ex->stream, ex->evUp, 0));
     }
-    ex->l0External = on_device != 0;
     // dword tile loads need 4-byte aligned rows; the slot pyramids always are, caller frames may not be
-    ex->l0Aligned = true;
-    if (on_device) {
-        if (stride & 3) ex->l0Aligned = false;
-        for (int b = 0; b < batch; b++)
-            if ((uintptr_t)images[b] & 3) ex->l0Aligned = false;
-    }
+    ex->l0Aligned = !on_device || ft_frames_aligned(images, batch, stride);
     ex->l0pitch = on_device ? stride : g.lv[0].pitch;
     ex->lastBatch = batch;
     FT_HIP(hipMemcpyAsync((void *)ex->d_l0, (const void *)ex->h_l0, sizeof(uint8_t *) * batch, hipMemcpyHostToDevice,
@@ -395,11 +317,40 @@ int ft_extract_prepare(ft_extractor *ex, const uint8_t *const *images, int batch
 
 // graph path with host frames: pinned staging for up to 8 slots (allocated once)
 int ft_extract_ensure_stage(ft_extractor *ex) {
-    if (!ex->h_srcTab) FT_HIP(hipHostMalloc((void **)&ex->h_srcTab, sizeof(FtSrcEntry) * 16, hipHostMallocDefault));
+    if (!ex->h_srcTab) FT_CHECK(ex->own.pinAlloc(&ex->h_srcTab, 16));
     // (up to 8 frames per camera; a paired stereo batch brings both cameras through one extractor)
-    if (!ex->h_stage)
-        FT_HIP(hipHostMalloc((void **)&ex->h_stage, (size_t)std::min(ex->maxBatch, 16) * ex->width * ex->height, hipHostMallocDefault));
+    if (!ex->h_stage) FT_CHECK(ex->own.pinAlloc(&ex->h_stage, (size_t)std::min(ex->maxBatch, 16) * ex->width * ex->height));
     return FT_OK;
+}
+bool ft_frames_aligned(const uint8_t *const *images, int batch, int stride) {
+    bool aligned = (stride & 3) == 0;
+    for (int b = 0; b < batch; b++)
+        if ((uintptr_t)images[b] & 3) aligned = false;
+    return aligned;
+}
+void ft_extract_rebind(ft_extractor *ex, const uint8_t *const *images, int batch, int on_device, int width, int height, int stride) {
+    if (on_device)
+        for (int b = 0; b < batch; b++) ex->h_l0[b] = images[b];
+    else
+        ft_extract_restage(ex, images, batch, width, height, stride);
+    ex->lastBatch = batch;
+}
+bool ft_graph_capture(hipStream_t st, hipGraphExec_t *exec, const std::function<int()> &enqueue) {
+    if (*exec) hipGraphExecDestroy(*exec);
+    *exec = nullptr;
+    hipGraph_t graph = nullptr;
+    int rc = FT_OK;
+    hipError_t ce = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+    if (ce == hipSuccess) {
+        rc = enqueue();
+        ce = hipStreamEndCapture(st, &graph);
+        if (rc == FT_OK && ce == hipSuccess && graph) ce = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+        if (graph) hipGraphDestroy(graph);
+    }
+    if (rc == FT_OK && ce == hipSuccess && *exec) return true;
+    (void)hipGetLastError();
+    *exec = nullptr;
+    return false;
 }
 // replay of a captured batch with host frames: refresh the staging copies the captured uploads read
 void ft_extract_restage(ft_extractor *ex, const uint8_t *const *images, int batch, int width, int height, int stride) {
@@ -422,8 +373,7 @@ void ft_extract_restage(ft_extractor *ex, const uint8_t *const *images, int batc
 // once the host octree is used - an extractor that stays on the device octree never allocates them.
 int ft_extract_ensure_host_cand(ft_extractor *ex) {
     if (ex->h_cand) return FT_OK;
-    const size_t n = std::max<size_t>((size_t)ex->maxBatch * ex->geom.candPerSlot, 1);
-    FT_HIP(hipHostMalloc((void **)&ex->h_cand, n * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+    FT_CHECK(ex->own.pinAlloc(&ex->h_cand, (size_t)ex->maxBatch * ex->geom.candPerSlot, hipHostMallocMapped | hipHostMallocCoherent));
     void *dp = nullptr;
     FT_HIP(hipHostGetDevicePointer(&dp, ex->h_cand, 0));
     ex->d_cand = (uint32_t *)dp;
@@ -513,6 +463,44 @@ int ft_extract_launch_octree(ft_extractor *ex, int sub, int b0, int nb, hipEvent
     return FT_OK;
 }
 
+// Host octree of one (slot, level): DistributeOctTree over `cand` [n], which must be in the reference's emission order (the
+// result depends on it), clamped to the level's bound, unpacked into the slot's selection.  Called from pool threads.
+static void hostOctreeLevel(ft_extractor *ex, int slot, int level, const uint32_t *cand, int n) {
+    static thread_local ft::OctreeWorkspace ws;
+    static thread_local std::vector<int> keep;
+    const FtLevelGeom &v = ex->geom.lv[level];
+    keep.clear();
+    const int minB = FT_EDGE_THRESHOLD - 3;
+    int k = ft::distribute_octree(cand, n, minB, v.maxBX, minB, v.maxBY, ex->quota[level], ws, keep);
+    k = std::min(k, ex->levelMax[level]);
+    FtSelKp *dst = ex->h_sel + (size_t)slot * ex->geom.maxKp + ex->levelOff[level];
+    for (int i = 0; i < k; i++) {
+        const uint32_t c = cand[keep[i]];
+        // ORBextractor.cc:1211-1217: add the border offset back
+        dst[i].x = (short)((c & 0xfffu) + minB);
+        dst[i].y = (short)(((c >> 12) & 0xfffu) + minB);
+        dst[i].level = (short)level;
+        dst[i].response = (short)(c >> 24);
+    }
+    ex->h_selCount[(size_t)slot * ex->nlevels + level] = k;
+}
+static void sumSelCounts(ft_extractor *ex, int slot) {
+    int n = 0;
+    for (int l = 0; l < ex->nlevels; l++) n += ex->h_selCount[(size_t)slot * ex->nlevels + l];
+    ex->h_nSel[slot] = n;
+}
+// The device stages deliver a level's candidates in arbitrary order (k_octree ranks them by their coordinates); this is the
+// reference's emission order: cell row, cell column, row-major inside the cell.
+static void sortEmissionOrder(const FtLevelGeom &v, uint32_t *cand, int n) {
+    auto rank = [&](uint32_t q) -> uint64_t {
+        const int x = (int)(q & 0xfffu) - 3, y = (int)((q >> 12) & 0xfffu) - 3;
+        const int cj = std::min(x / std::max(v.wCell, 1), std::max(v.nCols - 1, 0));
+        const int ci = std::min(y / std::max(v.hCell, 1), std::max(v.nRows - 1, 0));
+        return ((uint64_t)ci << 48) | ((uint64_t)cj << 32) | ((uint64_t)y << 16) | (uint64_t)x;
+    };
+    std::sort(cand, cand + n, [&](uint32_t a, uint32_t b) { return rank(a) < rank(b); });
+}
+
 // host octree over the candidates of slots [b0, b0+nb) of one or two extractors (their stage A must
 // have completed).  One task per (camera, level, image), issued level-major so the big level-0 trees
 // start first; results land in disjoint sub-ranges of a preallocated scratch and are packed per slot.
@@ -522,38 +510,15 @@ int ft_extract_octree_multi(ft_extractor *const *exs, int nex, int b0, int nb) {
     const int L = g.nlevels;
     const int perEx = nb * L;
     auto task = [&](int t, int) {
-        static thread_local ft::OctreeWorkspace ws;
-        static thread_local std::vector<int> keep;
         ft_extractor *ex = exs[t / perEx];
         const int r = t % perEx;
         const int level = r / nb, rel = r - level * nb, slot = b0 + rel;
-        const FtLevelGeom &v = g.lv[level];
-        const int n = ex->h_candCount[slot * L + level];
-        const uint32_t *cand = ex->h_cand + (size_t)slot * g.candPerSlot + v.candBase;
-        keep.clear();
-        const int minB = FT_EDGE_THRESHOLD - 3;
-        int k = ft::distribute_octree(cand, n, minB, v.maxBX, minB, v.maxBY, ex->quota[level], ws, keep);
-        k = std::min(k, ex->levelMax[level]);
-        FtSelKp *dst = ex->h_sel + (size_t)slot * g.maxKp + ex->levelOff[level];
-        for (int i = 0; i < k; i++) {
-            const uint32_t c = cand[keep[i]];
-            // ORBextractor.cc:1211-1217: add the border offset back
-            dst[i].x = (short)((c & 0xfffu) + minB);
-            dst[i].y = (short)(((c >> 12) & 0xfffu) + minB);
-            dst[i].level = (short)level;
-            dst[i].response = (short)(c >> 24);
-        }
-        ex->h_selCount[(size_t)slot * L + level] = k;
+        hostOctreeLevel(ex, slot, level, ex->h_cand + (size_t)slot * g.candPerSlot + g.lv[level].candBase,
+                        ex->h_candCount[slot * L + level]);
     };
     e0->ctx->pool->parallel_for(nex * perEx, task);
-    for (int e = 0; e < nex; e++) {
-        ft_extractor *ex = exs[e];
-        for (int slot = b0; slot < b0 + nb; slot++) {
-            int n = 0;
-            for (int l = 0; l < L; l++) n += ex->h_selCount[(size_t)slot * L + l];
-            ex->h_nSel[slot] = n;
-        }
-    }
+    for (int e = 0; e < nex; e++)
+        for (int slot = b0; slot < b0 + nb; slot++) sumSelCounts(exs[e], slot);
     return FT_OK;
 }
 
@@ -629,11 +594,10 @@ int ft_extract_repair_prepare(const std::vector<std::pair<ft_extractor *, int>> 
         for (auto &kv : perEx) {
             ft_extractor *ex = kv.first;
             if (kv.second > ex->repCap) {
-                if (ex->h_repCand) hipHostFree(ex->h_repCand);
-                ex->h_repCand = nullptr;
+                ex->own.giveBack(ex->h_repCand);
                 ex->repCap = 0;
                 const int want = std::min(ex->maxBatch, std::max(kv.second + kv.second / 2, 4));
-                FT_HIP(hipHostMalloc((void **)&ex->h_repCand, (size_t)want * g.candPerSlot * sizeof(uint32_t), hipHostMallocDefault));
+                FT_CHECK(ex->own.pinAlloc(&ex->h_repCand, (size_t)want * g.candPerSlot));
                 ex->repCap = want;
             }
         }
@@ -655,40 +619,16 @@ int ft_extract_repair_prepare(const std::vector<std::pair<ft_extractor *, int>> 
     }
     for (auto &j : jobs) FT_HIP(hipStreamSynchronize(j.first->streamB));
     auto task = [&](int t, int) {
-        static thread_local ft::OctreeWorkspace ws;
-        static thread_local std::vector<int> keep;
         const int j = t / L, level = t % L;
         ft_extractor *ex = jobs[j].first;
-        const int slot = jobs[j].second;
-        const FtLevelGeom &v = g.lv[level];
         const int n = counts[(size_t)j * L + level];
-        uint32_t *cand = ex->h_repCand + (size_t)jobIdx[j] * g.candPerSlot + v.candBase;
-        auto rank = [&](uint32_t q) -> uint64_t {
-            const int x = (int)(q & 0xfffu) - 3, y = (int)((q >> 12) & 0xfffu) - 3;
-            const int cj = std::min(x / std::max(v.wCell, 1), std::max(v.nCols - 1, 0));
-            const int ci = std::min(y / std::max(v.hCell, 1), std::max(v.nRows - 1, 0));
-            return ((uint64_t)ci << 48) | ((uint64_t)cj << 32) | ((uint64_t)y << 16) | (uint64_t)x;
-        };
-        std::sort(cand, cand + n, [&](uint32_t a, uint32_t b) { return rank(a) < rank(b); });
-        keep.clear();
-        const int minB = FT_EDGE_THRESHOLD - 3;
-        int k = ft::distribute_octree(cand, n, minB, v.maxBX, minB, v.maxBY, ex->quota[level], ws, keep);
-        k = std::min(k, ex->levelMax[level]);
-        FtSelKp *dst = ex->h_sel + (size_t)slot * g.maxKp + ex->levelOff[level];
-        for (int i = 0; i < k; i++) {
-            const uint32_t c = cand[keep[i]];
-            dst[i].x = (short)((c & 0xfffu) + minB);  // ORBextractor.cc:1211-1217: add the border offset back
-            dst[i].y = (short)(((c >> 12) & 0xfffu) + minB);
-            dst[i].level = (short)level;
-            dst[i].response = (short)(c >> 24);
-        }
-        ex->h_selCount[(size_t)slot * L + level] = k;
+        uint32_t *cand = ex->h_repCand + (size_t)jobIdx[j] * g.candPerSlot + g.lv[level].candBase;
+        sortEmissionOrder(g.lv[level], cand, n);
+        hostOctreeLevel(ex, jobs[j].second, level, cand, n);
     };
     e0->ctx->pool->parallel_for((int)jobs.size() * L, task);
     for (auto &j : jobs) {
-        int n = 0;
-        for (int l = 0; l < L; l++) n += j.first->h_selCount[(size_t)j.second * L + l];
-        j.first->h_nSel[j.second] = n;
+        sumSelCounts(j.first, j.second);
         j.first->ctx->addStat("extract.host_octree_repairs", 0);
     }
     return FT_OK;
@@ -745,6 +685,20 @@ int ft_extract_finish_counts(ft_extractor *ex, int batch, hipStream_t st) {
     a.batch = batch;
     a.nStreams = FT_OCT_STREAMS;
     return ft_launch_finish_counts(st, a);
+}
+
+FtDeliverArgs ft_deliver_args(const ft_extractor *ex) {
+    FtDeliverArgs d{};
+    d.keysL = ex->d_keys;
+    d.descL = ex->d_desc;
+    d.nL = ex->d_nSel;
+    d.overflowL = ex->d_overflow;
+    d.oKeysL = ex->h_keys;
+    d.oDescL = ex->h_desc;
+    d.oNL = ex->h_nSel;
+    d.oOverflowL = ex->h_overflow;
+    d.srcStride = d.dstStride = ex->geom.maxKp;
+    return d;
 }
 
 // async D2H of the keypoints / descriptors of slots [b0, b0+nb) on `st`
@@ -808,9 +762,9 @@ int ft_extractor_create(ft_context *ctx, int nfeatures, float scale_factor, int 
     FT_REQUIRE(image_width >= 2 * FT_EDGE_THRESHOLD + 8 && image_height >= 2 * FT_EDGE_THRESHOLD + 8,
                "image smaller than the 19-px border allows");
     FT_REQUIRE(max_batch >= 1 && max_batch <= 4096, "max_batch outside [1, 4096]");
-    int rc = ft_set_device(ctx);
-    if (rc != FT_OK) return rc;
+    FT_CHECK(ft_set_device(ctx));
     ft_extractor *ex = new ft_extractor();
+    std::unique_ptr<ft_extractor, void (*)(ft_extractor *)> guard(ex, destroyExtractor);  // (any early return)
     ex->ctx = ctx;
     ex->nfeatures = nfeatures;
     ex->scaleFactor = scale_factor;
@@ -822,11 +776,7 @@ int ft_extractor_create(ft_context *ctx, int nfeatures, float scale_factor, int 
     ex->maxBatch = max_batch;
     ex->tune = ctx->tuning;  // the extractor keeps the switches it was created under
     std::vector<FtTap> taps;
-    rc = buildGeometry(ex, taps);
-    if (rc != FT_OK) {
-        delete ex;
-        return rc;
-    }
+    FT_CHECK(buildGeometry(ex, taps));
     const FtGeom &g = ex->geom;
     const size_t B = max_batch;
     {  // the band plan of the one-launch pyramid
@@ -836,74 +786,51 @@ int ft_extractor_create(ft_context *ctx, int nfeatures, float scale_factor, int 
         for (int l = 1; l < g.nlevels; l++)
             for (int k = 0; k < PC_BANDS; k++) ex->pyrBands.rows[l][k] = (unsigned)first[l * PC_BANDS + k] | ((unsigned)end[l * PC_BANDS + k] << 16);
     }
-#define FT_TRY(x)            \
-    do {                     \
-        rc = (x);            \
-        if (rc != FT_OK) {   \
-            freeAll(ex);     \
-            delete ex;       \
-            return rc;       \
-        }                    \
-    } while (0)
     {
         hipStream_t lanes[FT_LANE_STREAMS];
         // latency-mode extractors (graph capture) own their streams; wide ones run on the context's lanes
-        FT_TRY(ft_context_take_lanes(ctx, max_batch <= 16, image_width, image_height, lanes, &ex->ownStreams));
+        FT_CHECK(ft_context_take_lanes(ctx, max_batch <= 16, image_width, image_height, lanes, &ex->ownStreams));
         ex->stream = lanes[0];
         ex->streamB = lanes[1];
         for (int i = 0; i < FT_OCT_STREAMS; i++) ex->streamO[i] = lanes[2 + i];
     }
-    hipError_t se = hipSuccess;
-    for (int i = 0; i < FT_PIPE_MAX && se == hipSuccess; i++) {
-        se = hipEventCreateWithFlags(&ex->evA[i], hipEventDisableTiming);
-        if (se == hipSuccess) se = hipEventCreateWithFlags(&ex->evB[i], hipEventDisableTiming);
-        if (se == hipSuccess) se = hipEventCreateWithFlags(&ex->evO[i], hipEventDisableTiming);
-        if (se == hipSuccess && i == 0) se = hipEventCreateWithFlags(&ex->evJoin, hipEventDisableTiming);
-        if (se == hipSuccess && i == 0) se = hipEventCreateWithFlags(&ex->evUp, hipEventDisableTiming);
+    FtOwned &own = ex->own;
+    for (int i = 0; i < FT_PIPE_MAX; i++) {
+        FT_CHECK(own.event(&ex->evA[i]));
+        FT_CHECK(own.event(&ex->evB[i]));
+        FT_CHECK(own.event(&ex->evO[i]));
     }
-    if (se != hipSuccess) {
-        freeAll(ex);
-        delete ex;
-        return ft_hip_fail(se, "stream / event creation", __FILE__, __LINE__);
-    }
-    FT_TRY(devAlloc(&ex->d_pyr, B * g.pyrPerSlot));
-    FT_TRY(devAlloc(&ex->d_taps, taps.size()));
-    FT_TRY(devAlloc(&ex->d_cellTab, (size_t)std::max(g.totalCells, 1)));
-    FT_TRY(devAlloc(&ex->d_cellCount, B * g.totalCells));
-    FT_TRY(devAlloc(&ex->d_stage, B * g.stagePerSlot));
-    FT_TRY(devAlloc(&ex->d_l0, B));
-    FT_TRY(devAlloc(&ex->d_sel, B * g.maxKp));
-    FT_TRY(devAlloc(&ex->d_nSel, B));
-    FT_TRY(devAlloc(&ex->d_selCount, B * g.nlevels + FT_MAX_LEVELS));  // k_orient_desc reads FT_MAX_LEVELS counts per image at once
-    FT_TRY(devAlloc(&ex->d_overflow, 1));
-    FT_TRY(devAlloc(&ex->d_ovSlot, B));
-    FT_TRY(devAlloc(&ex->d_bigCount, 4 * FT_OCT_STREAMS));
-    FT_TRY(pinAlloc(&ex->h_bigStat, FT_OCT_STREAMS));
-    FT_TRY(pinAlloc(&ex->h_histStat, FT_OCT_STREAMS));
+    FT_CHECK(own.event(&ex->evJoin));
+    FT_CHECK(own.event(&ex->evUp));
+    FT_CHECK(own.devAlloc(&ex->d_pyr, B * g.pyrPerSlot));
+    FT_CHECK(own.devAlloc(&ex->d_taps, taps.size()));
+    FT_CHECK(own.devAlloc(&ex->d_cellTab, (size_t)std::max(g.totalCells, 1)));
+    FT_CHECK(own.devAlloc(&ex->d_cellCount, B * g.totalCells));
+    FT_CHECK(own.devAlloc(&ex->d_stage, B * g.stagePerSlot));
+    FT_CHECK(own.devAlloc(&ex->d_l0, B));
+    FT_CHECK(own.devAlloc(&ex->d_sel, B * g.maxKp));
+    FT_CHECK(own.devAlloc(&ex->d_nSel, B));
+    FT_CHECK(own.devAlloc(&ex->d_selCount, B * g.nlevels + FT_MAX_LEVELS));  // k_orient_desc reads FT_MAX_LEVELS counts per image at once
+    FT_CHECK(own.devAlloc(&ex->d_overflow, 1));
+    FT_CHECK(own.devAlloc(&ex->d_ovSlot, B));
+    FT_CHECK(own.devAlloc(&ex->d_bigCount, 4 * FT_OCT_STREAMS));
+    FT_CHECK(own.pinAlloc(&ex->h_bigStat, FT_OCT_STREAMS));
+    FT_CHECK(own.pinAlloc(&ex->h_histStat, FT_OCT_STREAMS));
     for (int k = 0; k < FT_OCT_STREAMS; k++) ex->h_bigStat[k] = ex->h_histStat[k] = 0;
-    FT_TRY(devAlloc(&ex->d_bigList, (size_t)FT_OCT_STREAMS * B * g.nlevels));
-    FT_TRY(devAlloc(&ex->d_sortList, (size_t)FT_OCT_STREAMS * B * g.nlevels));
-    FT_TRY(pinAlloc(&ex->h_selCount, B * g.nlevels));
-    FT_TRY(pinAlloc(&ex->h_overflow, 1));
-    FT_TRY(devAlloc(&ex->d_keys, B * g.maxKp));
-    FT_TRY(devAlloc(&ex->d_desc, B * g.maxKp * 32));
-    FT_TRY(pinAlloc(&ex->h_l0, B));
-    FT_TRY(pinAlloc(&ex->h_candCount, B * g.nlevels, hipHostMallocMapped | hipHostMallocCoherent));
-    FT_TRY(pinAlloc(&ex->h_sel, B * g.maxKp));
-    FT_TRY(pinAlloc(&ex->h_nSel, B));
-    FT_TRY(pinAlloc(&ex->h_nMono, B));
-    FT_TRY(pinAlloc(&ex->h_keys, B * g.maxKp));
-    FT_TRY(pinAlloc(&ex->h_desc, B * g.maxKp * 32));
-    {
-        void *dp = nullptr;
-        hipError_t e = hipHostGetDevicePointer(&dp, ex->h_candCount, 0);
-        ex->d_candCount = (int *)dp;
-        if (e != hipSuccess) {
-            freeAll(ex);
-            delete ex;
-            return ft_hip_fail(e, "hipHostGetDevicePointer", __FILE__, __LINE__);
-        }
-    }
+    FT_CHECK(own.devAlloc(&ex->d_bigList, (size_t)FT_OCT_STREAMS * B * g.nlevels));
+    FT_CHECK(own.devAlloc(&ex->d_sortList, (size_t)FT_OCT_STREAMS * B * g.nlevels));
+    FT_CHECK(own.pinAlloc(&ex->h_selCount, B * g.nlevels));
+    FT_CHECK(own.pinAlloc(&ex->h_overflow, 1));
+    FT_CHECK(own.devAlloc(&ex->d_keys, B * g.maxKp));
+    FT_CHECK(own.devAlloc(&ex->d_desc, B * g.maxKp * 32));
+    FT_CHECK(own.pinAlloc(&ex->h_l0, B));
+    FT_CHECK(own.pinAlloc(&ex->h_candCount, B * g.nlevels, hipHostMallocMapped | hipHostMallocCoherent));
+    FT_CHECK(own.pinAlloc(&ex->h_sel, B * g.maxKp));
+    FT_CHECK(own.pinAlloc(&ex->h_nSel, B));
+    FT_CHECK(own.pinAlloc(&ex->h_nMono, B));
+    FT_CHECK(own.pinAlloc(&ex->h_keys, B * g.maxKp));
+    FT_CHECK(own.pinAlloc(&ex->h_desc, B * g.maxKp * 32));
+    FT_HIP(hipHostGetDevicePointer((void **)&ex->d_candCount, ex->h_candCount, 0));
     {
         std::vector<FtCellRec> cellTab(std::max(g.totalCells, 1), FtCellRec{0, 0, 0, 0});
         for (int l = 0; l < nlevels; l++) {
@@ -924,14 +851,9 @@ int ft_extractor_create(ft_context *ctx, int nfeatures, float scale_factor, int 
                     r.outOff = (uint32_t)(v.stageBase + c * v.cellCap);
                 }
         }
-        hipError_t e = hipMemcpy(ex->d_cellTab, cellTab.data(), cellTab.size() * sizeof(FtCellRec), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(ex->d_taps, taps.data(), taps.size() * sizeof(FtTap), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(ex->d_nSel, 0, sizeof(int) * B);
-        if (e != hipSuccess) {
-            freeAll(ex);
-            delete ex;
-            return ft_hip_fail(e, "upload resize tables", __FILE__, __LINE__);
-        }
+        FT_HIP(hipMemcpy(ex->d_cellTab, cellTab.data(), cellTab.size() * sizeof(FtCellRec), hipMemcpyHostToDevice));
+        FT_HIP(hipMemcpy(ex->d_taps, taps.data(), taps.size() * sizeof(FtTap), hipMemcpyHostToDevice));
+        FT_HIP(hipMemset(ex->d_nSel, 0, sizeof(int) * B));
     }
     memset(ex->h_nSel, 0, sizeof(int) * B);
     ex->levelOff.assign(nlevels + 1, 0);
@@ -968,27 +890,21 @@ int ft_extractor_create(ft_context *ctx, int nfeatures, float scale_factor, int 
         o.low = nullptr;  // set per launch (ft_extract_launch_octree)
         if (ex->deviceOctree) {
             if (ft_debug_env("FT_DEBUG_OCT_PROFILE")) {  // per-level phase clocks of k_octree (slot 0) kept on the device
-                FT_TRY(devAlloc(&o.prof, (size_t)FT_MAX_LEVELS * 8));
+                FT_CHECK(own.devAlloc(&o.prof, (size_t)FT_MAX_LEVELS * 8));
                 hipMemset(o.prof, 0, sizeof(unsigned long long) * FT_MAX_LEVELS * 8);
             }
-            FT_TRY(devAlloc(&ex->d_candDev, B * g.candPerSlot));
-            FT_TRY(devAlloc(&ex->d_candCountDev, B * g.nlevels));
+            FT_CHECK(own.devAlloc(&ex->d_candDev, B * g.candPerSlot));
+            FT_CHECK(own.devAlloc(&ex->d_candCountDev, B * g.nlevels));
             // the first sorted tier in the compact LDS layout (49 instead of 64 KB per workgroup) wherever it fits
             if (ft_octree_smem_bytes(o.poolCap, true) < ft_octree_smem_bytes(o.poolCap, false))
-                FT_TRY(devAlloc(&ex->d_octLow, B * g.nlevels * (size_t)FT_OCT_MAXN));
-            hipError_t me = hipMemset(ex->d_overflow, 0, sizeof(int));
-            if (me == hipSuccess) me = hipMemset(ex->d_ovSlot, 0, sizeof(int) * B);
-            if (me == hipSuccess) me = hipMemset(ex->d_bigCount, 0, 4 * FT_OCT_STREAMS * sizeof(int));
-            if (me != hipSuccess) {
-                freeAll(ex);
-                delete ex;
-                return ft_hip_fail(me, "hipMemset", __FILE__, __LINE__);
-            }
+                FT_CHECK(own.devAlloc(&ex->d_octLow, B * g.nlevels * (size_t)FT_OCT_MAXN));
+            FT_HIP(hipMemset(ex->d_overflow, 0, sizeof(int)));
+            FT_HIP(hipMemset(ex->d_ovSlot, 0, sizeof(int) * B));
+            FT_HIP(hipMemset(ex->d_bigCount, 0, 4 * FT_OCT_STREAMS * sizeof(int)));
         }
     }
-#undef FT_TRY
     ctx->liveObjects++;
-    *out = ex;
+    *out = guard.release();
     return FT_OK;
 }
 
@@ -1131,9 +1047,7 @@ int ft_extract_batch(ft_extractor *ex, const uint8_t *const *images, int batch, 
     if (rc != FT_OK) return rc;
     const int S = ft_pipeline_depth(ex->tune, batch, ex->deviceOctree);
     const int sb = (batch + S - 1) / S;
-    // everything a batch needs with the device octree, enqueued without a host synchronisation (capture != 0: ex->stream is
-    // being captured into a graph; the octree / stage-B streams fork from it through events and are joined back)
-    const bool deliver = batch <= 8;  // (FtDeliverArgs, ft_internal.h)
+    const bool deliver = batch <= 8;  // small enough for one kernel to deliver the results (FtDeliverArgs, ft_internal.h)
     // a wide batch whose output arrays lie in pinned memory of this context (ft_host_malloc): the device writes the results there
     // itself, in the reference's output order (k_deliver_ordered) - no staging copy, no pass of the host over the keypoints
     static const bool stagedOnly = ft_debug_env("FT_DEBUG_STAGED_OUTPUTS") != nullptr;  // (A/B aid: the staging copy + the host's pass)
@@ -1157,153 +1071,35 @@ int ft_extract_batch(ft_extractor *ex, const uint8_t *const *images, int batch, 
         a.lap1 = (float)lap1;
         return ft_launch_deliver_ordered(ex->streamB, nb, a);
     };
-    auto enqueueDevice = [&](int capture) -> int {
-        int r = ft_extract_prepare(ex, images, batch, on_device, width, height, stride);
-        if (r != FT_OK) return r;
-        for (int s = 0, b0 = 0; b0 < batch; s++, b0 += sb) {
-            const int nb = std::min(sb, batch - b0);
-            r = ft_extract_launch_a(ex, b0, nb, nullptr);
-            if (r == FT_OK) r = ft_extract_launch_octree(ex, s, b0, nb, ex->evA[s]);
-            if (r != FT_OK) return r;
-        }
-        for (int s = 0, b0 = 0; b0 < batch; s++, b0 += sb) {
-            const int nb = std::min(sb, batch - b0);
-            FT_HIP(hipStreamWaitEvent(ex->streamB, ex->evA[s], 0));
-            r = ft_extract_launch_b(ex, b0, nb, ex->streamB);
-            if (r == FT_OK && !deliver) r = ft_extract_download(ex, b0, nb, ex->streamB);
-            if (r != FT_OK) return r;
-        }
-        if (deliver) {  // latency mode: one kernel writes keypoints, descriptors and counters to the pinned staging
-            FtDeliverArgs d;
-            memset(&d, 0, sizeof d);
-            d.keysL = ex->d_keys;
-            d.descL = ex->d_desc;
-            d.nL = ex->d_nSel;
-            d.overflowL = ex->d_overflow;
-            d.oKeysL = ex->h_keys;
-            d.oDescL = ex->h_desc;
-            d.oNL = ex->h_nSel;
-            d.oOverflowL = ex->h_overflow;
-            d.srcStride = d.dstStride = ex->geom.maxKp;
-            r = ft_launch_deliver(ex->streamB, batch, d);
-        } else {
-            r = ft_extract_finish_counts(ex, batch, ex->streamB);
-        }
-        if (r != FT_OK) return r;
-        if (capture) {
-            FT_HIP(hipEventRecord(ex->evJoin, ex->streamB));
-            FT_HIP(hipStreamWaitEvent(ex->stream, ex->evJoin, 0));
-        }
-        return FT_OK;
-    };
     // images with a level beyond the device octree's limits (seen after the batch has drained): each is redone with the
     // host octree in place, the rest of the batch keeps its device results
     auto repairOverflow = [&]() -> int {
         std::vector<int> slots;
-        int r = ft_extract_overflow_slots(ex, batch, slots);
-        if (r != FT_OK) return r;
+        FT_CHECK(ft_extract_overflow_slots(ex, batch, slots));
         std::vector<std::pair<ft_extractor *, int>> jobs;
         for (int b : slots) jobs.emplace_back(ex, b);
-        r = ft_extract_repair_prepare(jobs);
-        if (r != FT_OK) return r;
+        FT_CHECK(ft_extract_repair_prepare(jobs));
         for (int b : slots) {
             ex->ctx->addStat("extract.device_octree_fallbacks", 1);
-            r = ft_extract_repair_launch(ex, b, ex->streamB);
-            if (r == FT_OK) r = deliveredDirect ? deliverOrdered(b, 1) : ft_extract_download(ex, b, 1, ex->streamB);
-            if (r != FT_OK) return r;
+            FT_CHECK(ft_extract_repair_launch(ex, b, ex->streamB));
+            FT_CHECK(deliveredDirect ? deliverOrdered(b, 1) : ft_extract_download(ex, b, 1, ex->streamB));
         }
         FT_HIP(hipStreamSynchronize(ex->streamB));
         return FT_OK;
     };
-    bool done = false;
-    const bool devWanted = ex->deviceOctree;
-    const bool graphsOn = ex->tune.graph != 0;
-    if (graphsOn && !ex->graphDisabled && ex->ownStreams && ex->deviceOctree && !ex->ctx->kernelTiming && batch >= 1 && batch <= 8 &&
-        batch <= ex->maxBatch && width == ex->width && height == ex->height && stride >= width) {
-        bool ok = true;
-        for (int b = 0; b < batch; b++)
-            if (!images[b]) ok = false;
-        if (ok) {
-            ft_extractor::GraphKey key;
-            key.batch = batch; key.onDevice = on_device; key.width = width; key.height = height; key.stride = stride;
-            key.aligned = 1;
-            key.bigGrid = ex->bigGrid + (ex->histOn ? (1 << 24) : 0);
-            if (on_device) {
-                if (stride & 3) key.aligned = 0;
-                for (int b = 0; b < batch; b++)
-                    if ((uintptr_t)images[b] & 3) key.aligned = 0;
-            } else if (ft_extract_ensure_stage(ex) != FT_OK) {
-                ok = false;
-                (void)hipGetLastError();
-            }
-            bool launched = false;
-            if (!ok) {
-            } else if (ex->graphExec && key == ex->graphKey) {
-                if (on_device)
-                    for (int b = 0; b < batch; b++) ex->h_l0[b] = images[b];
-                else
-                    ft_extract_restage(ex, images, batch, width, height, stride);
-                ex->lastBatch = batch;
-                FT_HIP(hipGraphLaunch(ex->graphExec, ex->stream));
-                launched = true;
-            } else {
-                if (ex->graphExec) {
-                    hipGraphExecDestroy(ex->graphExec);
-                    ex->graphExec = nullptr;
-                }
-                hipGraph_t graph = nullptr;
-                ex->stageHost = !on_device;
-                hipError_t ce = hipStreamBeginCapture(ex->stream, hipStreamCaptureModeThreadLocal);
-                if (ce == hipSuccess) {
-                    rc = enqueueDevice(1);
-                    ce = hipStreamEndCapture(ex->stream, &graph);
-                    if (rc == FT_OK && ce == hipSuccess && graph) ce = hipGraphInstantiate(&ex->graphExec, graph, nullptr, nullptr, 0);
-                    if (graph) hipGraphDestroy(graph);
-                }
-                if (rc != FT_OK || ce != hipSuccess || !ex->graphExec) {
-                    (void)hipGetLastError();  // capture is an optimisation: plain enqueueing from now on
-                    ex->graphDisabled = true;
-                    ex->graphExec = nullptr;
-                    ex->ctx->addStat("extract.graph_capture_failed", 0);
-                    rc = FT_OK;
-                    ex->stageHost = false;
-                } else {
-                    ex->stageHost = false;
-                    ex->graphKey = key;
-                    ex->ctx->addStat("extract.graph_captures", 0);
-                    FT_HIP(hipGraphLaunch(ex->graphExec, ex->stream));
-                    launched = true;
-                }
-            }
-            if (launched) {
-                ex->ctx->addStat("extract.device_octree_batches", 0);
-                FT_HIP(hipStreamSynchronize(ex->stream));
-                ft_extract_update_big_grid(ex);
-                if (ex->h_overflow[0]) {  // some image met a level beyond the device octree's limits: that image is repaired
-                    rc = repairOverflow();
-                    if (rc != FT_OK) return rc;
-                }
-                done = true;
-            }
-        }
-    }
-    if (!done) {
-        rc = ft_extract_prepare(ex, images, batch, on_device, width, height, stride);
-        if (rc != FT_OK) return rc;
-    }
-    if (!done) {
-        const bool dev = ex->deviceOctree;
-        if (dev) ex->ctx->addStat("extract.device_octree_batches", 0);
+    // The whole batch, sub-batch by sub-batch.  With the device octree nothing waits for the host; with the host octree the
+    // octree of one sub-batch runs between its stages while the GPU is busy with the next.  capture: ex->stream is being
+    // captured into a graph (device octree, at most 8 frames) - the octree and stage-B streams fork from it through events
+    // and are joined back, and one kernel writes keypoints, descriptors and counters to the pinned staging at the end.
+    const bool dev = ex->deviceOctree;
+    double tOct = 0;
+    auto enqueue = [&](bool capture) -> int {
+        FT_CHECK(ft_extract_prepare(ex, images, batch, on_device, width, height, stride));
         for (int s = 0, b0 = 0; b0 < batch; s++, b0 += sb) {
             const int nb = std::min(sb, batch - b0);
-            rc = ft_extract_launch_a(ex, b0, nb, dev ? nullptr : ex->evA[s]);
-            if (rc != FT_OK) return rc;
-            if (dev) {
-                rc = ft_extract_launch_octree(ex, s, b0, nb, ex->evA[s]);
-                if (rc != FT_OK) return rc;
-            }
+            FT_CHECK(ft_extract_launch_a(ex, b0, nb, dev ? nullptr : ex->evA[s]));
+            if (dev) FT_CHECK(ft_extract_launch_octree(ex, s, b0, nb, ex->evA[s]));
         }
-        double tOct = 0;
         for (int s = 0, b0 = 0; b0 < batch; s++, b0 += sb) {
             const int nb = std::min(sb, batch - b0);
             if (dev) {
@@ -1311,28 +1107,59 @@ int ft_extract_batch(ft_extractor *ex, const uint8_t *const *images, int batch, 
             } else {
                 FT_HIP(hipEventSynchronize(ex->evA[s]));
                 FtTimer tO;
-                rc = ft_extract_octree(ex, b0, nb);
-                if (rc != FT_OK) return rc;
+                FT_CHECK(ft_extract_octree(ex, b0, nb));
                 tOct += tO.ms();
             }
-            rc = ft_extract_launch_b(ex, b0, nb, ex->streamB);
-            if (rc != FT_OK) return rc;
-            rc = (direct && dev) ? deliverOrdered(b0, nb) : ft_extract_download(ex, b0, nb, ex->streamB);
-            if (rc != FT_OK) return rc;
+            FT_CHECK(ft_extract_launch_b(ex, b0, nb, ex->streamB));
+            if (!capture) FT_CHECK((direct && dev) ? deliverOrdered(b0, nb) : ft_extract_download(ex, b0, nb, ex->streamB));
         }
-        rc = ft_extract_finish_counts(ex, batch, ex->streamB);
-        if (rc != FT_OK) return rc;
+        if (!capture) return ft_extract_finish_counts(ex, batch, ex->streamB);
+        FT_CHECK(ft_launch_deliver(ex->streamB, batch, ft_deliver_args(ex)));
+        FT_HIP(hipEventRecord(ex->evJoin, ex->streamB));
+        FT_HIP(hipStreamWaitEvent(ex->stream, ex->evJoin, 0));
+        return FT_OK;
+    };
+    // latency mode: a small batch with a fixed call shape is captured once as a graph and replayed
+    bool launched = false, graphable = ex->tune.graph != 0 && !ex->graphDisabled && ex->ownStreams && dev && !ex->ctx->kernelTiming &&
+                                       deliver && batch >= 1 && batch <= ex->maxBatch && width == ex->width && height == ex->height && stride >= width;
+    for (int b = 0; b < batch && graphable; b++)
+        if (!images[b]) graphable = false;
+    if (graphable && !on_device && ft_extract_ensure_stage(ex) != FT_OK) {
+        (void)hipGetLastError();
+        graphable = false;
+    }
+    if (graphable) {
+        ft_extractor::GraphKey key;
+        key.batch = batch; key.onDevice = on_device; key.width = width; key.height = height; key.stride = stride;
+        key.aligned = !on_device || ft_frames_aligned(images, batch, stride);
+        key.bigGrid = ex->bigGrid + (ex->histOn ? (1 << 24) : 0);
+        if (ex->graphExec && key == ex->graphKey) {
+            ft_extract_rebind(ex, images, batch, on_device, width, height, stride);
+            launched = true;
+        } else {
+            ex->stageHost = !on_device;  // (ft_extract_prepare: host frames go through the pinned staging)
+            launched = ft_graph_capture(ex->stream, &ex->graphExec, [&] { return enqueue(true); });
+            ex->stageHost = false;
+            ex->graphDisabled = !launched;  // capture is an optimisation: plain enqueueing from now on
+            if (launched) ex->graphKey = key;
+            ex->ctx->addStat(launched ? "extract.graph_captures" : "extract.graph_capture_failed", 0);
+        }
+    }
+    if (launched) FT_HIP(hipGraphLaunch(ex->graphExec, ex->stream));
+    else FT_CHECK(enqueue(false));
+    if (dev) ex->ctx->addStat("extract.device_octree_batches", 0);  // (the host's bookkeeping runs while the GPU works)
+    if (launched) {
+        FT_HIP(hipStreamSynchronize(ex->stream));
+    } else {
         FT_HIP(hipStreamSynchronize(ex->streamB));
         FT_HIP(hipStreamSynchronize(ex->stream));
         ex->evt.resolve(ex->ctx);
         if (!dev) ex->ctx->addStat("extract.octree(host)", tOct);
-        if (dev) ft_extract_update_big_grid(ex);
-        if (dev && ex->h_overflow[0]) {
-            rc = repairOverflow();
-            if (rc != FT_OK) return rc;
-        }
     }
-    ex->deviceOctree = devWanted;
+    if (dev) {
+        ft_extract_update_big_grid(ex);
+        if (ex->h_overflow[0]) FT_CHECK(repairOverflow());  // an image met a level beyond the device octree's limits: it is repaired
+    }
     if (deliveredDirect) {  // (the arrays are filled; what is left is the counts)
         for (int b = 0; b < batch; b++)
             if (ex->h_nSel[b] > capacity) {
@@ -1434,16 +1261,7 @@ int ft_extractor_download_candidates(ft_extractor *ex, int slot, int level, int 
         tmp.resize(std::max(cnt, 1));
         FT_HIP(hipMemcpy(tmp.data(), ex->d_candDev + (size_t)slot * g.candPerSlot + g.lv[level].candBase,
                          sizeof(uint32_t) * cnt, hipMemcpyDeviceToHost));
-        // the device path delivers every cell's candidates in arbitrary order (k_octree ranks them by their
-        // coordinates); present them in the reference's emission order: cell row, cell column, row-major in the cell
-        const FtLevelGeom &L = g.lv[level];
-        auto rank = [&](uint32_t v) -> uint64_t {
-            const int x = (int)(v & 0xfffu) - 3, y = (int)((v >> 12) & 0xfffu) - 3;
-            const int cj = std::min(x / std::max(L.wCell, 1), std::max(L.nCols - 1, 0));
-            const int ci = std::min(y / std::max(L.hCell, 1), std::max(L.nRows - 1, 0));
-            return ((uint64_t)ci << 48) | ((uint64_t)cj << 32) | ((uint64_t)y << 16) | (uint64_t)x;
-        };
-        std::sort(tmp.begin(), tmp.begin() + cnt, [&](uint32_t a, uint32_t b) { return rank(a) < rank(b); });
+        sortEmissionOrder(g.lv[level], tmp.data(), cnt);  // (presented as the host path would have delivered them)
         c = tmp.data();
     }
     *n = cnt;

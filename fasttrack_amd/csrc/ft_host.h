@@ -1,8 +1,10 @@
 // Host-side object definitions behind the opaque C handles.
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -11,6 +13,20 @@
 #include "ft_internal.h"
 #include "octree.h"
 #include "thread_pool.h"
+
+// argument checks of the C entry points, and "pass an error code on"
+#define FT_REQUIRE(cond, msg)               \
+    do {                                    \
+        if (!(cond)) {                      \
+            ft_set_error(std::string(msg)); \
+            return FT_ERR_INVALID;          \
+        }                                   \
+    } while (0)
+#define FT_CHECK(call)                \
+    do {                              \
+        const int _rc = (call);       \
+        if (_rc != FT_OK) return _rc; \
+    } while (0)
 
 #define FT_PIPE_MAX 8
 // Streams of an extractor: stage A, stage B and FT_OCT_STREAMS octree streams (a long, thin k_octree never sits in front
@@ -145,6 +161,54 @@ struct FtEventTimer {
     }
 };
 
+// What an object holds on the device side - device memory, pinned host memory, events - recorded as it is made and released
+// together: a buffer is named where it is allocated and nowhere else.
+struct FtOwned {
+    std::vector<void *> dev, pin;
+    std::vector<hipEvent_t> events;
+    FtOwned() = default;
+    FtOwned(const FtOwned &) = delete;
+    FtOwned &operator=(const FtOwned &) = delete;
+    ~FtOwned() { release(); }
+    template <typename T>
+    int devAlloc(T **p, size_t n) {
+        FT_HIP(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
+        dev.push_back((void *)*p);
+        return FT_OK;
+    }
+    template <typename T>
+    int pinAlloc(T **p, size_t n, unsigned flags = hipHostMallocDefault) {
+        FT_HIP(hipHostMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T), flags));
+        pin.push_back((void *)*p);
+        return FT_OK;
+    }
+    int event(hipEvent_t *e) {  // (ordering only: no timestamps)
+        FT_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        events.push_back(*e);
+        return FT_OK;
+    }
+    template <typename T>
+    void giveBack(T *&p) {  // one buffer early (grow-only scratch about to be replaced by a larger one)
+        auto drop = [&](std::vector<void *> &v) {
+            auto it = std::find(v.begin(), v.end(), (void *)p);
+            if (it == v.end()) return false;
+            v.erase(it);
+            return true;
+        };
+        if (p && drop(dev)) hipFree((void *)p);
+        else if (p && drop(pin)) hipHostFree((void *)p);
+        p = nullptr;
+    }
+    void release() {
+        for (auto e : events) hipEventDestroy(e);
+        for (auto p : dev) hipFree(p);
+        for (auto p : pin) hipHostFree(p);
+        events.clear();
+        dev.clear();
+        pin.clear();
+    }
+};
+
 struct FtTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     double ms() const {
@@ -170,6 +234,7 @@ struct ft_extractor {
     // so that the wide stage-A kernels of the following sub-batches are not queued behind it
     hipStream_t streamO[FT_OCT_STREAMS] = {};
     bool ownStreams = false;  // false: the streams are lanes of the context
+    FtOwned own;              // every buffer and event below
     hipEvent_t evO[FT_PIPE_MAX] = {};
     // latency mode of ft_extract / ft_extract_batch: a small batch with a fixed call shape is captured once as a HIP
     // graph (see ft_stereo_frontend::GraphKey); the key is everything baked into the nodes
@@ -198,7 +263,6 @@ struct ft_extractor {
     uint8_t *h_stage = nullptr;      // pinned staging of host frames for the graph path (up to 16 slots, allocated on first use)
     FtSrcEntry *h_srcTab = nullptr;  // pinned: where k_upload finds each frame (the caller's pinned memory or h_stage)
     bool stageHost = false;          // ft_extract_prepare: host frames go through h_stage (their pointers may change between replays)
-    float *d_sf = nullptr;           // scale factors on device [nlevels] then inverse [nlevels]
     // host-mapped pinned buffers written by the device
     uint32_t *h_cand = nullptr, *d_cand = nullptr;
     int *h_candCount = nullptr, *d_candCount = nullptr;
@@ -232,17 +296,12 @@ struct ft_extractor {
     ft_keypoint *d_keys = nullptr, *h_keys = nullptr;
     uint8_t *d_desc = nullptr, *h_desc = nullptr;
     // scratch of the host-array stereo API (ft_stereo_match), allocated on first use
-    ft_keypoint *d_stKeys = nullptr;  // [2 * maxKp] left then right
-    uint8_t *d_stDesc = nullptr;      // [2 * maxKp * 32]
-    float *d_stOut = nullptr;         // [2 * maxKp] uright then depth
-    int *d_stInt = nullptr;           // [2 * stCap + 4] sad, hamming idx, then nL nR nMatches, then the row starts, then [stCap] left order
-    FtSortedR *d_stSorted = nullptr;  // [stCap] right keypoints in row-bucket order
+    uint8_t *d_stScratch = nullptr;  // one allocation for stCap keypoints per camera, carved by ft_stereo_match
     int stCap = 0;
     FtEventTimer evt;
     // state of the last call (consumed by the stereo matcher)
     int lastBatch = 0;
     int l0pitch = 0;
-    bool l0External = false;
     bool l0Aligned = true;
 };
 
@@ -251,6 +310,7 @@ struct ft_stereo_frontend {
     ft_extractor *exL = nullptr, *exR = nullptr;
     float mbf = 0, mb = 0;
     int capacity = 0;
+    FtOwned own;  // the buffers and events below (the extractors own theirs)
     float *d_uright = nullptr, *d_depth = nullptr, *h_uright = nullptr, *h_depth = nullptr;
     int *d_sad = nullptr, *d_nMatches = nullptr, *h_nMatches = nullptr;
     // Latency front ends (max_batch <= 8): the left extractor is created with room for 2 x max_batch images and a small
@@ -262,7 +322,6 @@ struct ft_stereo_frontend {
     FtSortedR *d_sorted = nullptr;  // right keypoints bucketed by row (k_stereo_rowsort)
     int *d_rowStart = nullptr;
     int *d_leftOrder = nullptr;     // left keypoint indices in row order (k_stereo_rowsort)
-    hipEvent_t evR = nullptr;
     // Latency mode: a small batch with a fixed call shape (same sizes, same result arrays, same kind of input) is
     // captured once as a HIP graph - ~45 enqueue calls on seven streams become one launch.  graphKey holds everything
     // that is baked into the captured nodes.
@@ -316,6 +375,16 @@ int ft_extract_launch_a(ft_extractor *ex, int b0, int nb, hipEvent_t done);
 int ft_extract_ensure_stage(ft_extractor *ex);
 int ft_extract_ensure_host_cand(ft_extractor *ex);
 void ft_extract_restage(ft_extractor *ex, const uint8_t *const *images, int batch, int width, int height, int stride);
+// Latency mode, shared by ft_extract_batch and the stereo front end.  ft_graph_capture: what `enqueue` puts on `st` (and on the
+// streams it forks from `st` and joins back) becomes *exec, in place of an older one; false: nothing was instantiated, *exec is
+// null and the runtime's error is cleared - capture is an optimisation, the caller enqueues plainly from then on.
+bool ft_graph_capture(hipStream_t st, hipGraphExec_t *exec, const std::function<int()> &enqueue);
+bool ft_frames_aligned(const uint8_t *const *images, int batch, int stride);  // device frames: rows take dword loads
+// replay of a captured batch: the new frames reach the captured nodes through the level-0 pointer table (device frames) or
+// the pinned staging and source table (host frames)
+void ft_extract_rebind(ft_extractor *ex, const uint8_t *const *images, int batch, int on_device, int width, int height, int stride);
+// FtDeliverArgs, value-initialised, with the left camera's fields: the extractor's results into its own pinned staging
+FtDeliverArgs ft_deliver_args(const ft_extractor *ex);
 int ft_extract_octree(ft_extractor *ex, int b0, int nb);
 int ft_extract_overflow_slots(ft_extractor *ex, int batch, std::vector<int> &slots);
 void ft_extract_update_big_grid(ft_extractor *ex);

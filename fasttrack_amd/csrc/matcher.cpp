@@ -3,23 +3,68 @@
 // fused extract+match front end used for throughput.  All compute is in kernels_match.hip.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 
 #include "ft_host.h"
 
 #define FT_GRAPH_MAX_BATCH 8  // latency mode: batches up to this size are captured as graphs / run paired
 
-#define FT_REQUIRE(cond, msg)               \
-    do {                                    \
-        if (!(cond)) {                      \
-            ft_set_error(std::string(msg)); \
-            return FT_ERR_INVALID;          \
-        }                                   \
-    } while (0)
-
 static bool sameGeometry(const ft_extractor *a, const ft_extractor *b) {
     return a->width == b->width && a->height == b->height && a->nlevels == b->nlevels &&
            a->scaleFactor == b->scaleFactor && a->ctx == b->ctx;
 }
+
+// one camera's input of the stereo match (device): keypoints, descriptors (n x 32), count(s)
+struct StereoSide {
+    const ft_keypoint *keys;
+    const uint8_t *desc;
+    const int *n;
+};
+// FtStereoArgs from the two cameras' arrays (`capacity` records between images), the outputs, the row buffers and the rig
+static FtStereoArgs stereoArgs(StereoSide l, StereoSide r, int capacity, float *uright, float *depth, int *sad, int *hamIdx, int *nMatches,
+                               int medianCut, int *rowStart, int rowStride, FtSortedR *sorted, int *leftOrder, float mbf, float mb,
+                               bool aligned) {
+    FtStereoArgs a{};
+    a.keysL = l.keys;
+    a.keysR = r.keys;
+    a.descL = l.desc;
+    a.descR = r.desc;
+    a.nL = l.n;
+    a.nR = r.n;
+    a.capacity = capacity;
+    a.mbf = mbf;
+    a.mb = mb;
+    a.uright = uright;
+    a.depth = depth;
+    a.sad = sad;
+    a.hamIdx = hamIdx;
+    a.nMatches = nMatches;
+    a.applyMedianCut = medianCut;
+    a.rowStart = rowStart;
+    a.sorted = sorted;
+    a.rowStride = rowStride;
+    a.leftOrder = leftOrder;
+    a.alignedLoads = aligned;
+    return a;
+}
+
+// ft_stereo_match's device scratch for C keypoints per camera: one allocation, every array 256 bytes aligned
+struct StereoScratch {
+    size_t keys, desc, out, ints, sorted, total = 0;
+    StereoScratch(int C, int height) {
+        auto take = [&](size_t bytes) {
+            const size_t o = total;
+            total = (total + bytes + 255) & ~(size_t)255;
+            return o;
+        };
+        keys = take(sizeof(ft_keypoint) * 2 * C);  // left then right
+        desc = take((size_t)64 * C);
+        out = take(sizeof(float) * 2 * C);  // uright then depth
+        // sad, hamming idx, then nL nR nMatches (+ pad), then the row starts, then the left order
+        ints = take(sizeof(int) * (3 * (size_t)C + 8 + height + 2));
+        sorted = take(sizeof(FtSortedR) * (size_t)C);  // right keypoints in row-bucket order
+    }
+};
 
 extern "C" {
 
@@ -43,66 +88,38 @@ int ft_stereo_match(ft_extractor *exL, ft_extractor *exR, int slot, const ft_key
     static_assert(sizeof(ft_keypoint) == 28, "ft_keypoint must match cv::KeyPoint");
     // device scratch for the host arrays: grows to the largest request
     const int need = std::max(cap, g.maxKp);
-    if (!exL->d_stKeys || need > exL->stCap) {
-        hipFree(exL->d_stKeys);
-        hipFree(exL->d_stDesc);
-        hipFree(exL->d_stOut);
-        hipFree(exL->d_stInt);
-        hipFree(exL->d_stSorted);
-        exL->d_stSorted = nullptr;
-        exL->d_stKeys = nullptr;
-        exL->d_stDesc = nullptr;
-        exL->d_stOut = nullptr;
-        exL->d_stInt = nullptr;
-        FT_HIP(hipMalloc((void **)&exL->d_stKeys, sizeof(ft_keypoint) * 2 * need));
-        FT_HIP(hipMalloc((void **)&exL->d_stDesc, (size_t)64 * need));
-        FT_HIP(hipMalloc((void **)&exL->d_stOut, sizeof(float) * 2 * need));
-        FT_HIP(hipMalloc((void **)&exL->d_stInt, sizeof(int) * (3 * (size_t)need + 8 + exL->height + 2)));
-        FT_HIP(hipMalloc((void **)&exL->d_stSorted, sizeof(FtSortedR) * (size_t)need));
+    if (need > exL->stCap) {
+        exL->own.giveBack(exL->d_stScratch);
+        exL->stCap = 0;
+        FT_CHECK(exL->own.devAlloc(&exL->d_stScratch, StereoScratch(need, exL->height).total));
         exL->stCap = need;
     }
     const int C = exL->stCap;
+    const StereoScratch o(C, exL->height);
+    ft_keypoint *dKeys = (ft_keypoint *)(exL->d_stScratch + o.keys);
+    uint8_t *dDesc = exL->d_stScratch + o.desc;
+    float *dOut = (float *)(exL->d_stScratch + o.out);
+    int *dInt = (int *)(exL->d_stScratch + o.ints), *d_hdr = dInt + 2 * C;
     hipStream_t st = exL->stream;
     FT_HIP(hipStreamSynchronize(exR->stream));  // right pyramid must be complete
     FT_HIP(hipStreamSynchronize(exR->streamB));
     FT_HIP(hipStreamSynchronize(exL->streamB));
-    FT_HIP(hipMemcpyAsync(exL->d_stKeys, keysL, sizeof(ft_keypoint) * nL, hipMemcpyHostToDevice, st));
-    FT_HIP(hipMemcpyAsync(exL->d_stDesc, descL, (size_t)32 * nL, hipMemcpyHostToDevice, st));
+    FT_HIP(hipMemcpyAsync(dKeys, keysL, sizeof(ft_keypoint) * nL, hipMemcpyHostToDevice, st));
+    FT_HIP(hipMemcpyAsync(dDesc, descL, (size_t)32 * nL, hipMemcpyHostToDevice, st));
     if (nR > 0) {
-        FT_HIP(hipMemcpyAsync(exL->d_stKeys + C, keysR, sizeof(ft_keypoint) * nR, hipMemcpyHostToDevice, st));
-        FT_HIP(hipMemcpyAsync(exL->d_stDesc + (size_t)32 * C, descR, (size_t)32 * nR, hipMemcpyHostToDevice, st));
+        FT_HIP(hipMemcpyAsync(dKeys + C, keysR, sizeof(ft_keypoint) * nR, hipMemcpyHostToDevice, st));
+        FT_HIP(hipMemcpyAsync(dDesc + (size_t)32 * C, descR, (size_t)32 * nR, hipMemcpyHostToDevice, st));
     }
-    int hdr[4] = {nL, nR, 0, 0};
-    int *d_hdr = exL->d_stInt + 2 * C;
+    const int hdr[4] = {nL, nR, 0, 0};
     FT_HIP(hipMemcpyAsync(d_hdr, hdr, sizeof hdr, hipMemcpyHostToDevice, st));
-    FtStereoArgs a;
-    a.keysL = exL->d_stKeys;
-    a.keysR = exL->d_stKeys + C;
-    a.descL = exL->d_stDesc;
-    a.descR = exL->d_stDesc + (size_t)32 * C;
-    a.nL = d_hdr;
-    a.nR = d_hdr + 1;
-    a.capacity = C;  // single pair: stride is irrelevant but bounds the grid
-    a.mbf = mbf;
-    a.mb = mb;
-    a.uright = exL->d_stOut;
-    a.depth = exL->d_stOut + C;
-    a.sad = exL->d_stInt;
-    a.hamIdx = exL->d_stInt + C;
-    a.nMatches = d_hdr + 2;
-    a.applyMedianCut = apply_median_cut;
-    a.sorted = exL->d_stSorted;
-    a.rowStart = exL->d_stInt + 2 * C + 4;
-    a.rowStride = exL->height + 2;
-    a.leftOrder = a.rowStart + a.rowStride;
-    a.alignedLoads = exL->l0Aligned && exR->l0Aligned;
-    rc = ft_launch_stereo_rowsort(st, g, 1, a);
-    if (rc != FT_OK) return rc;
-    rc = ft_launch_stereo_match(st, g, 1, exL->d_l0 + slot, exR->d_l0 + slot, exL->l0pitch, exR->l0pitch,
-                                exL->d_pyr + (size_t)slot * g.pyrPerSlot, exR->d_pyr + (size_t)slot * g.pyrPerSlot, a);
-    if (rc != FT_OK) return rc;
-    rc = ft_launch_stereo_median(st, 1, a);
-    if (rc != FT_OK) return rc;
+    // (capacity C: a single pair, the stride is irrelevant but bounds the grid)
+    FtStereoArgs a = stereoArgs({dKeys, dDesc, d_hdr}, {dKeys + C, dDesc + (size_t)32 * C, d_hdr + 1}, C, dOut, dOut + C, dInt, dInt + C,
+                                d_hdr + 2, apply_median_cut, d_hdr + 4, exL->height + 2, (FtSortedR *)(exL->d_stScratch + o.sorted),
+                                d_hdr + 4 + exL->height + 2, mbf, mb, exL->l0Aligned && exR->l0Aligned);
+    FT_CHECK(ft_launch_stereo_rowsort(st, g, 1, a));
+    FT_CHECK(ft_launch_stereo_match(st, g, 1, exL->d_l0 + slot, exR->d_l0 + slot, exL->l0pitch, exR->l0pitch,
+                                    exL->d_pyr + (size_t)slot * g.pyrPerSlot, exR->d_pyr + (size_t)slot * g.pyrPerSlot, a));
+    FT_CHECK(ft_launch_stereo_median(st, 1, a));
     FT_HIP(hipMemcpyAsync(uright, a.uright, sizeof(float) * nL, hipMemcpyDeviceToHost, st));
     FT_HIP(hipMemcpyAsync(depth, a.depth, sizeof(float) * nL, hipMemcpyDeviceToHost, st));
     if (sad) FT_HIP(hipMemcpyAsync(sad, a.sad, sizeof(int) * nL, hipMemcpyDeviceToHost, st));
@@ -120,42 +137,34 @@ int ft_stereo_frontend_create(ft_context *ctx, int nfeatures, float scale_factor
     FT_REQUIRE(ctx && out, "ft_stereo_frontend_create: null argument");
     *out = nullptr;
     ft_stereo_frontend *fe = new ft_stereo_frontend();
+    std::unique_ptr<ft_stereo_frontend, int (*)(ft_stereo_frontend *)> guard(fe, ft_stereo_frontend_destroy);  // (any early return)
     fe->ctx = ctx;
     fe->mbf = mbf;
     fe->mb = mb;
     fe->maxBatch = max_batch;
     const bool pairedOn = ctx->tuning.paired != 0;
     fe->pairedCapable = pairedOn && max_batch >= 1 && max_batch <= FT_GRAPH_MAX_BATCH;
-    int rc = ft_extractor_create(ctx, nfeatures, scale_factor, nlevels, ini_th_fast, min_th_fast, image_width,
-                                 image_height, fe->pairedCapable ? 2 * max_batch : max_batch, &fe->exL);
-    if (rc == FT_OK)
-        rc = ft_extractor_create(ctx, nfeatures, scale_factor, nlevels, ini_th_fast, min_th_fast, image_width,
-                                 image_height, max_batch, &fe->exR);
-    if (rc != FT_OK) {
-        ft_stereo_frontend_destroy(fe);
-        return rc;
-    }
+    FT_CHECK(ft_extractor_create(ctx, nfeatures, scale_factor, nlevels, ini_th_fast, min_th_fast, image_width, image_height,
+                                 fe->pairedCapable ? 2 * max_batch : max_batch, &fe->exL));
+    FT_CHECK(ft_extractor_create(ctx, nfeatures, scale_factor, nlevels, ini_th_fast, min_th_fast, image_width, image_height,
+                                 max_batch, &fe->exR));
     fe->capacity = fe->exL->geom.maxKp;
     const size_t n = (size_t)max_batch * fe->capacity;
-    hipError_t e = hipMalloc((void **)&fe->d_uright, sizeof(float) * n);
-    if (e == hipSuccess) e = hipMalloc((void **)&fe->d_depth, sizeof(float) * n);
-    if (e == hipSuccess) e = hipMalloc((void **)&fe->d_sad, sizeof(int) * n);
-    if (e == hipSuccess) e = hipMalloc((void **)&fe->d_nMatches, sizeof(int) * max_batch);
-    if (e == hipSuccess) e = hipMalloc((void **)&fe->d_sorted, sizeof(FtSortedR) * n);
-    if (e == hipSuccess) e = hipMalloc((void **)&fe->d_rowStart, sizeof(int) * (size_t)max_batch * (image_height + 2));
-    if (e == hipSuccess) e = hipMalloc((void **)&fe->d_leftOrder, sizeof(int) * n);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&fe->h_uright, sizeof(float) * n, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&fe->h_depth, sizeof(float) * n, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&fe->h_nMatches, sizeof(int) * max_batch, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&fe->evR, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&fe->evFork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&fe->evJoin, hipEventDisableTiming);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&fe->evDone[i], hipEventDisableTiming);
-    if (e != hipSuccess) {
-        ft_stereo_frontend_destroy(fe);
-        return ft_hip_fail(e, "stereo frontend allocation", __FILE__, __LINE__);
-    }
-    *out = fe;
+    FtOwned &own = fe->own;
+    FT_CHECK(own.devAlloc(&fe->d_uright, n));
+    FT_CHECK(own.devAlloc(&fe->d_depth, n));
+    FT_CHECK(own.devAlloc(&fe->d_sad, n));
+    FT_CHECK(own.devAlloc(&fe->d_nMatches, max_batch));
+    FT_CHECK(own.devAlloc(&fe->d_sorted, n));
+    FT_CHECK(own.devAlloc(&fe->d_rowStart, (size_t)max_batch * (image_height + 2)));
+    FT_CHECK(own.devAlloc(&fe->d_leftOrder, n));
+    FT_CHECK(own.pinAlloc(&fe->h_uright, n));
+    FT_CHECK(own.pinAlloc(&fe->h_depth, n));
+    FT_CHECK(own.pinAlloc(&fe->h_nMatches, max_batch));
+    FT_CHECK(own.event(&fe->evFork));
+    FT_CHECK(own.event(&fe->evJoin));
+    for (int i = 0; i < 2; i++) FT_CHECK(own.event(&fe->evDone[i]));
+    *out = guard.release();
     return FT_OK;
 }
 
@@ -164,22 +173,8 @@ int ft_stereo_frontend_destroy(ft_stereo_frontend *fe) {
     hipSetDevice(fe->ctx->device);
     ft_extractor_destroy(fe->exL);
     ft_extractor_destroy(fe->exR);
-    hipFree(fe->d_uright);
-    hipFree(fe->d_depth);
-    hipFree(fe->d_sad);
-    hipFree(fe->d_nMatches);
-    hipFree(fe->d_sorted);
-    hipFree(fe->d_rowStart);
-    hipFree(fe->d_leftOrder);
-    hipHostFree(fe->h_uright);
-    hipHostFree(fe->h_depth);
-    hipHostFree(fe->h_nMatches);
-    if (fe->evR) hipEventDestroy(fe->evR);
-    if (fe->evFork) hipEventDestroy(fe->evFork);
-    if (fe->evJoin) hipEventDestroy(fe->evJoin);
-    for (int i = 0; i < 2; i++)
-        if (fe->evDone[i]) hipEventDestroy(fe->evDone[i]);
     if (fe->graphExec) hipGraphExecDestroy(fe->graphExec);
+    fe->own.release();
     delete fe;
     return FT_OK;
 }
@@ -187,9 +182,44 @@ int ft_stereo_frontend_destroy(ft_stereo_frontend *fe) {
 ft_extractor *ft_stereo_frontend_left(ft_stereo_frontend *fe) { return fe ? fe->exL : nullptr; }
 ft_extractor *ft_stereo_frontend_right(ft_stereo_frontend *fe) { return fe ? fe->exR : nullptr; }
 
-// result arrays in pinned host memory (ft_host_malloc) are filled by the D2H copies directly
-static bool isPinnedHost(const void *p) { return ft_is_pinned_host(p); }
-
+// The front end's match from slot b0 on: the left camera in the left extractor's arrays, the right one in `r` - the right
+// extractor's, or the upper half of the left extractor's in a paired batch.
+static FtStereoArgs frontendStereoArgs(const ft_stereo_frontend *fe, int b0, StereoSide r, bool aligned) {
+    const ft_extractor *L = fe->exL;
+    const int maxKp = L->geom.maxKp, rowStride = L->height + 2;
+    const size_t o = (size_t)b0 * maxKp;
+    return stereoArgs({L->d_keys + o, L->d_desc + o * 32, L->d_nSel + b0}, r, maxKp, fe->d_uright + o, fe->d_depth + o, fe->d_sad + o,
+                      nullptr, fe->d_nMatches + b0, 1, fe->d_rowStart + (size_t)b0 * rowStride, rowStride, fe->d_sorted + o,
+                      fe->d_leftOrder + o, fe->mbf, fe->mb, aligned);
+}
+// Delivery of a whole small batch by one kernel: `r` and `overflowR` as above; the host side of the right camera is always
+// the right extractor's (in a paired batch it only lends its pinned staging and counters).  direct: the rows go to the
+// caller's pinned arrays (`capacity` records per image) instead of the staging.
+static FtDeliverArgs frontendDeliverArgs(const ft_stereo_frontend *fe, StereoSide r, const int *overflowR, bool direct, ft_keypoint *keysL,
+                                         uint8_t *descL, ft_keypoint *keysR, uint8_t *descR, float *uright, float *depth, int capacity) {
+    const ft_extractor *L = fe->exL, *R = fe->exR;
+    FtDeliverArgs d = ft_deliver_args(L);
+    d.keysR = r.keys;
+    d.descR = r.desc;
+    d.nR = r.n;
+    d.overflowR = overflowR;
+    d.uright = fe->d_uright;
+    d.depth = fe->d_depth;
+    d.nMatches = fe->d_nMatches;
+    if (direct) {
+        d.oKeysL = keysL;
+        d.oDescL = descL;
+        d.dstStride = capacity;
+    }
+    d.oKeysR = direct ? keysR : R->h_keys;
+    d.oDescR = direct ? descR : R->h_desc;
+    d.oUright = direct ? uright : fe->h_uright;
+    d.oDepth = direct ? depth : fe->h_depth;
+    d.oNR = R->h_nSel;
+    d.oNMatches = fe->h_nMatches;
+    d.oOverflowR = R->h_overflow;
+    return d;
+}
 
 // Matching and result copies of the slots [b0, b0 + nb) once their descriptors are enqueued on the stage-B streams of the
 // two extractors: row sort, stereo match, median cut on the left stage-B stream, then (unless one kernel delivers the whole
@@ -222,27 +252,7 @@ static int frontendMatchAndDeliver(ft_stereo_frontend *fe, int s, int b0, int nb
     // keypoints stay on the device between extraction and matching: pinhole stereo passes the lapping
     // area (0,0) (src/Frame.cc:127), no keypoint has x == 0, so mono order == extraction order.
     const size_t o = (size_t)b0 * g.maxKp;
-    FtStereoArgs a;
-    a.keysL = L->d_keys + o;
-    a.keysR = R->d_keys + o;
-    a.descL = L->d_desc + o * 32;
-    a.descR = R->d_desc + o * 32;
-    a.nL = L->d_nSel + b0;
-    a.nR = R->d_nSel + b0;
-    a.capacity = g.maxKp;
-    a.mbf = fe->mbf;
-    a.mb = fe->mb;
-    a.uright = fe->d_uright + o;
-    a.depth = fe->d_depth + o;
-    a.sad = fe->d_sad + o;
-    a.hamIdx = nullptr;
-    a.nMatches = fe->d_nMatches + b0;
-    a.applyMedianCut = 1;
-    a.rowStride = L->height + 2;
-    a.rowStart = fe->d_rowStart + (size_t)b0 * a.rowStride;
-    a.sorted = fe->d_sorted + o;
-    a.leftOrder = fe->d_leftOrder + o;
-    a.alignedLoads = L->l0Aligned && R->l0Aligned;
+    const FtStereoArgs a = frontendStereoArgs(fe, b0, {R->d_keys + o, R->d_desc + o * 32, R->d_nSel + b0}, L->l0Aligned && R->l0Aligned);
     L->evt.begin(tm, "kernel.stereo_rowsort", st);
     rc = ft_launch_stereo_rowsort(st, g, nb, a);
     L->evt.end(tm, st);
@@ -295,70 +305,21 @@ static int frontendEnqueue(ft_stereo_frontend *fe, const uint8_t *const *imagesL
         const int B = batch;
         std::vector<const uint8_t *> imgs(imagesL, imagesL + B);
         imgs.insert(imgs.end(), imagesR, imagesR + B);
-        int rc = ft_extract_prepare(L, imgs.data(), 2 * B, on_device, width, height, stride);
-        if (rc != FT_OK) return rc;
+        FT_CHECK(ft_extract_prepare(L, imgs.data(), 2 * B, on_device, width, height, stride));
         fe->ctx->addStat("stereo.device_octree_batches", 0);
-        rc = ft_extract_launch_a(L, 0, 2 * B, nullptr);
-        if (rc == FT_OK) rc = ft_extract_launch_octree(L, 0, 0, 2 * B, L->evA[0]);
-        if (rc != FT_OK) return rc;
+        FT_CHECK(ft_extract_launch_a(L, 0, 2 * B, nullptr));
+        FT_CHECK(ft_extract_launch_octree(L, 0, 0, 2 * B, L->evA[0]));
         hipStream_t st = L->streamB;
         FT_HIP(hipStreamWaitEvent(st, L->evA[0], 0));
-        rc = ft_extract_launch_b(L, 0, 2 * B, st);
-        if (rc != FT_OK) return rc;
+        FT_CHECK(ft_extract_launch_b(L, 0, 2 * B, st));
         const size_t oR = (size_t)B * g.maxKp;  // the right camera's half of the left extractor's arrays
-        FtStereoArgs a;
-        a.keysL = L->d_keys;
-        a.keysR = L->d_keys + oR;
-        a.descL = L->d_desc;
-        a.descR = L->d_desc + oR * 32;
-        a.nL = L->d_nSel;
-        a.nR = L->d_nSel + B;
-        a.capacity = g.maxKp;
-        a.mbf = fe->mbf;
-        a.mb = fe->mb;
-        a.uright = fe->d_uright;
-        a.depth = fe->d_depth;
-        a.sad = fe->d_sad;
-        a.hamIdx = nullptr;
-        a.nMatches = fe->d_nMatches;
-        a.applyMedianCut = 1;
-        a.rowStride = L->height + 2;
-        a.rowStart = fe->d_rowStart;
-        a.sorted = fe->d_sorted;
-        a.leftOrder = fe->d_leftOrder;
-        a.alignedLoads = L->l0Aligned;
-        rc = ft_launch_stereo_rowsort(st, g, B, a);
-        if (rc == FT_OK)
-            rc = ft_launch_stereo_match(st, g, B, L->d_l0, L->d_l0 + B, L->l0pitch, L->l0pitch, L->d_pyr,
-                                        L->d_pyr + (size_t)B * g.pyrPerSlot, a);
-        if (rc == FT_OK) rc = ft_launch_stereo_median(st, B, a);
-        if (rc != FT_OK) return rc;
-        FtDeliverArgs d;
-        d.keysL = a.keysL;
-        d.keysR = a.keysR;
-        d.descL = a.descL;
-        d.descR = a.descR;
-        d.uright = fe->d_uright;
-        d.depth = fe->d_depth;
-        d.nL = a.nL;
-        d.nR = a.nR;
-        d.nMatches = fe->d_nMatches;
-        d.overflowL = d.overflowR = L->d_overflow;
-        d.oKeysL = direct ? keysL : L->h_keys;
-        d.oKeysR = direct ? keysR : R->h_keys;  // the right extractor lends its pinned staging and counters
-        d.oDescL = direct ? descL : L->h_desc;
-        d.oDescR = direct ? descR : R->h_desc;
-        d.oUright = direct ? uright : fe->h_uright;
-        d.oDepth = direct ? depth : fe->h_depth;
-        d.oNL = L->h_nSel;
-        d.oNR = R->h_nSel;
-        d.oNMatches = fe->h_nMatches;
-        d.oOverflowL = L->h_overflow;
-        d.oOverflowR = R->h_overflow;
-        d.srcStride = g.maxKp;
-        d.dstStride = direct ? capacity : g.maxKp;
-        rc = ft_launch_deliver(st, B, d);
-        if (rc != FT_OK) return rc;
+        const StereoSide right = {L->d_keys + oR, L->d_desc + oR * 32, L->d_nSel + B};
+        const FtStereoArgs a = frontendStereoArgs(fe, 0, right, L->l0Aligned);
+        FT_CHECK(ft_launch_stereo_rowsort(st, g, B, a));
+        FT_CHECK(ft_launch_stereo_match(st, g, B, L->d_l0, L->d_l0 + B, L->l0pitch, L->l0pitch, L->d_pyr,
+                                        L->d_pyr + (size_t)B * g.pyrPerSlot, a));
+        FT_CHECK(ft_launch_stereo_median(st, B, a));
+        FT_CHECK(ft_launch_deliver(st, B, frontendDeliverArgs(fe, right, L->d_overflow, direct, keysL, descL, keysR, descR, uright, depth, capacity)));
         R->lastBatch = B;
         if (capture) {
             FT_HIP(hipEventRecord(fe->evJoin, st));
@@ -425,37 +386,11 @@ static int frontendEnqueue(ft_stereo_frontend *fe, const uint8_t *const *imagesL
         tLaunch += tL.ms();
     }
     if (deliver) {
-        FtDeliverArgs d;
-        d.keysL = L->d_keys;
-        d.keysR = R->d_keys;
-        d.descL = L->d_desc;
-        d.descR = R->d_desc;
-        d.uright = fe->d_uright;
-        d.depth = fe->d_depth;
-        d.nL = L->d_nSel;
-        d.nR = R->d_nSel;
-        d.nMatches = fe->d_nMatches;
-        d.overflowL = L->d_overflow;
-        d.overflowR = R->d_overflow;
-        d.oKeysL = direct ? keysL : L->h_keys;
-        d.oKeysR = direct ? keysR : R->h_keys;
-        d.oDescL = direct ? descL : L->h_desc;
-        d.oDescR = direct ? descR : R->h_desc;
-        d.oUright = direct ? uright : fe->h_uright;
-        d.oDepth = direct ? depth : fe->h_depth;
-        d.oNL = L->h_nSel;
-        d.oNR = R->h_nSel;
-        d.oNMatches = fe->h_nMatches;
-        d.oOverflowL = L->h_overflow;
-        d.oOverflowR = R->h_overflow;
-        d.srcStride = g.maxKp;
-        d.dstStride = direct ? capacity : g.maxKp;
-        rc = ft_launch_deliver(st, batch, d);
-        if (rc != FT_OK) return rc;
+        FT_CHECK(ft_launch_deliver(st, batch, frontendDeliverArgs(fe, {R->d_keys, R->d_desc, R->d_nSel}, R->d_overflow, direct, keysL, descL,
+                                                                  keysR, descR, uright, depth, capacity)));
     } else {
-        rc = ft_extract_finish_counts(L, batch, st);
-        if (rc == FT_OK) rc = ft_extract_finish_counts(R, batch, st);
-        if (rc != FT_OK) return rc;
+        FT_CHECK(ft_extract_finish_counts(L, batch, st));
+        FT_CHECK(ft_extract_finish_counts(R, batch, st));
     }
     if (capture) {  // join: the stage-B stream of the left camera is the tail of everything
         FT_HIP(hipEventRecord(fe->evJoin, st));
@@ -488,17 +423,18 @@ int ft_stereo_frontend_submit(ft_stereo_frontend *fe, const uint8_t *const *imag
     if (rc != FT_OK) return rc;
     const bool dev = L->deviceOctree && R->deviceOctree;
     const bool paired = fe->pairedCapable && dev && batch <= FT_GRAPH_MAX_BATCH && 2 * batch <= L->maxBatch;
-    const bool direct = isPinnedHost(keysL) && isPinnedHost(descL) && isPinnedHost(keysR) && isPinnedHost(descR) &&
-                        isPinnedHost(uright) && isPinnedHost(depth) && (!dev || capacity >= g.maxKp);
+    // result arrays in pinned host memory (ft_host_malloc) are filled by the device directly
+    const bool direct = ft_is_pinned_host(keysL) && ft_is_pinned_host(descL) && ft_is_pinned_host(keysR) && ft_is_pinned_host(descR) &&
+                        ft_is_pinned_host(uright) && ft_is_pinned_host(depth) && (!dev || capacity >= g.maxKp);
     // ---- latency mode: small batches with a fixed call shape run as one captured graph ----
-    const bool graphsOn = fe->exL->tune.graph != 0;
-    bool useGraph = graphsOn && !fe->graphDisabled && L->ownStreams && R->ownStreams && dev && direct && !fe->ctx->kernelTiming && batch >= 1 &&
-                    batch <= FT_GRAPH_MAX_BATCH && batch <= fe->maxBatch && width == L->width && height == L->height &&
-                    stride >= width;
-    bool launched = false;
-    if (useGraph) {
-        for (int b = 0; b < batch; b++)
-            if (!imagesL[b] || !imagesR[b]) useGraph = false;
+    bool launched = false, useGraph = L->tune.graph != 0 && !fe->graphDisabled && L->ownStreams && R->ownStreams && dev && direct &&
+                                      !fe->ctx->kernelTiming && batch <= FT_GRAPH_MAX_BATCH && width == L->width && height == L->height &&
+                                      stride >= width;
+    for (int b = 0; b < batch && useGraph; b++)
+        if (!imagesL[b] || !imagesR[b]) useGraph = false;
+    if (useGraph && !on_device && (ft_extract_ensure_stage(L) != FT_OK || ft_extract_ensure_stage(R) != FT_OK)) {
+        (void)hipGetLastError();
+        useGraph = false;
     }
     if (useGraph) {
         ft_stereo_frontend::GraphKey key;
@@ -507,80 +443,38 @@ int ft_stereo_frontend_submit(ft_stereo_frontend *fe, const uint8_t *const *imag
         key.paired = paired ? 1 : 0;
         key.bigGridL = L->bigGrid + (L->histOn ? (1 << 24) : 0);
         key.bigGridR = R->bigGrid + (R->histOn ? (1 << 24) : 0);
-        key.alignedL = key.alignedR = 1;
-        if (on_device) {
-            if (stride & 3) key.alignedL = key.alignedR = 0;
-            for (int b = 0; b < batch; b++) {
-                if ((uintptr_t)imagesL[b] & 3) key.alignedL = 0;
-                if ((uintptr_t)imagesR[b] & 3) key.alignedR = 0;
-            }
-            if (paired) key.alignedL = key.alignedR = key.alignedL & key.alignedR;  // one launch reads both cameras
-        } else if (ft_extract_ensure_stage(L) != FT_OK || ft_extract_ensure_stage(R) != FT_OK) {
-            (void)hipGetLastError();
-            useGraph = false;
-        }
+        key.alignedL = !on_device || ft_frames_aligned(imagesL, batch, stride);
+        key.alignedR = !on_device || ft_frames_aligned(imagesR, batch, stride);
+        if (paired) key.alignedL = key.alignedR = key.alignedL & key.alignedR;  // one launch reads both cameras
         const void *outs[6] = {keysL, descL, keysR, descR, uright, depth};
         for (int i = 0; i < 6; i++) key.out[i] = outs[i];
-        if (!useGraph) {
-        } else if (fe->graphExec && key == fe->graphKey) {
-            // replay: device frames change through the level-0 pointer tables, host frames through the pinned staging
-            // the captured uploads read
-            if (paired) {
+        if (fe->graphExec && key == fe->graphKey) {
+            if (paired) {  // (both cameras in the left extractor: frontendEnqueue)
                 std::vector<const uint8_t *> imgs(imagesL, imagesL + batch);
                 imgs.insert(imgs.end(), imagesR, imagesR + batch);
-                if (on_device)
-                    for (int b = 0; b < 2 * batch; b++) L->h_l0[b] = imgs[b];
-                else
-                    ft_extract_restage(L, imgs.data(), 2 * batch, width, height, stride);
-                L->lastBatch = 2 * batch;
+                ft_extract_rebind(L, imgs.data(), 2 * batch, on_device, width, height, stride);
                 R->lastBatch = batch;
-                fe->lastPaired = true;
             } else {
-                if (on_device) {
-                    for (int b = 0; b < batch; b++) {
-                        L->h_l0[b] = imagesL[b];
-                        R->h_l0[b] = imagesR[b];
-                    }
-                } else {
-                    ft_extract_restage(L, imagesL, batch, width, height, stride);
-                    ft_extract_restage(R, imagesR, batch, width, height, stride);
-                }
-                L->lastBatch = R->lastBatch = batch;
-                fe->lastPaired = false;
+                ft_extract_rebind(L, imagesL, batch, on_device, width, height, stride);
+                ft_extract_rebind(R, imagesR, batch, on_device, width, height, stride);
             }
+            fe->lastPaired = paired;
             fe->ctx->addStat("stereo.device_octree_batches", 0);
             FtTimer tG;
             FT_HIP(hipGraphLaunch(fe->graphExec, L->stream));
             fe->ctx->addStat("stereo.graph_launch", tG.ms());
             launched = true;
         } else {
-            if (fe->graphExec) {
-                hipGraphExecDestroy(fe->graphExec);
-                fe->graphExec = nullptr;
-            }
-            hipGraph_t graph = nullptr;
-            L->stageHost = R->stageHost = !on_device;
-            hipError_t ce = hipStreamBeginCapture(L->stream, hipStreamCaptureModeThreadLocal);
-            if (ce == hipSuccess) {
-                rc = frontendEnqueue(fe, imagesL, imagesR, batch, on_device, width, height, stride, keysL, descL, nL, keysR,
-                                     descR, nR, capacity, uright, depth, n_matches, direct, 1, paired);
-                ce = hipStreamEndCapture(L->stream, &graph);
-                if (rc == FT_OK && ce == hipSuccess && graph) ce = hipGraphInstantiate(&fe->graphExec, graph, nullptr, nullptr, 0);
-                if (graph) hipGraphDestroy(graph);
-            }
+            L->stageHost = R->stageHost = !on_device;  // (ft_extract_prepare: host frames go through the pinned staging)
+            launched = ft_graph_capture(L->stream, &fe->graphExec, [&] {
+                return frontendEnqueue(fe, imagesL, imagesR, batch, on_device, width, height, stride, keysL, descL, nL, keysR, descR, nR,
+                                       capacity, uright, depth, n_matches, direct, 1, paired);
+            });
             L->stageHost = R->stageHost = false;
-            if (rc != FT_OK || ce != hipSuccess || !fe->graphExec) {
-                // capture is an optimisation: fall back to plain enqueueing for good
-                (void)hipGetLastError();
-                fe->graphDisabled = true;
-                fe->graphExec = nullptr;
-                fe->ctx->addStat("stereo.graph_capture_failed", 0);
-            } else {
-                fe->graphKey = key;
-                fe->ctx->addStat("stereo.graph_captures", 0);
-                FT_HIP(hipGraphLaunch(fe->graphExec, L->stream));
-                launched = true;
-            }
+            fe->graphDisabled = !launched;  // capture is an optimisation: plain enqueueing for good
+            if (launched) fe->graphKey = key;
+            fe->ctx->addStat(launched ? "stereo.graph_captures" : "stereo.graph_capture_failed", 0);
+            if (launched) FT_HIP(hipGraphLaunch(fe->graphExec, L->stream));
         }
     }
     if (!launched) {

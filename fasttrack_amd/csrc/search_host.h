@@ -14,14 +14,6 @@
 #include "ft_host.h"
 #include "ft_search.h"
 
-#define FT_REQUIRE(cond, msg)               \
-    do {                                    \
-        if (!(cond)) {                      \
-            ft_set_error(std::string(msg)); \
-            return FT_ERR_INVALID;          \
-        }                                   \
-    } while (0)
-
 struct Arena {
     size_t off = 0;
     size_t take(size_t bytes) {

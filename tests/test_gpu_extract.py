@@ -269,6 +269,58 @@ def _calls(ctx, name):
         return 0
 
 
+_GRAPH_CASE = {}
+
+
+def _graph_case():
+    """seven different 320x240 images (three calls of two, one call of one) and the oracle's result for each, computed once"""
+    if not _GRAPH_CASE:
+        w, h, nf = 320, 240, 500
+        imgs = [synth.make_image(w, h, seed=900 + i) for i in range(7)]
+        _GRAPH_CASE.update(w=w, h=h, nf=nf, imgs=imgs, ref=[ob.Extractor(nf).extract(im)[:2] for im in imgs])
+    return _GRAPH_CASE
+
+
+@pytest.mark.parametrize("frames", ["pageable", "pinned", "device"])
+def test_extract_graph_replay(ctx, frames):
+    """latency mode of ft_extract_batch: a small batch with a fixed call shape is captured once as a HIP graph and replayed.
+    Every call brings other images in other buffers - pageable host arrays (copied into the pinned staging), pinned host arrays
+    (read where they are) or frames resident in HBM (through the level-0 pointer table) - so a replay that did not rebind its
+    inputs returns the previous call's keypoints.  A different batch size is a different graph."""
+    c = _graph_case()
+    w, h, imgs, ref = c["w"], c["h"], c["imgs"], c["ref"]
+    ex = orb.ORBextractor(ctx, c["nf"], 1.2, 8, 20, 7, w, h, max_batch=4)
+
+    def buffer(im):
+        if frames == "device":
+            return ctx.to_device(im)
+        if frames == "pinned":
+            p = ctx.pinned_array((h, w), np.uint8)
+            p[:] = im
+            return p
+        return im.copy()
+
+    def run(idx):
+        bufs = [buffer(imgs[i]) for i in idx]
+        if frames == "device":
+            res = ex.extract_batch(bufs, on_device=True, width=w, height=h, stride=w)
+        else:
+            res = ex.extract_batch(bufs)
+        for i, (gk, gd, _) in zip(idx, res):
+            _check_same(gk, gd, ref[i][0], ref[i][1])
+
+    failed0, c0 = _calls(ctx, "extract.graph_capture_failed"), _calls(ctx, "extract.graph_captures")
+    for k in range(3):
+        run([2 * k, 2 * k + 1])
+    captured = _calls(ctx, "extract.graph_capture_failed") == failed0
+    if captured:
+        assert _calls(ctx, "extract.graph_captures") == c0 + 1, "the call shape did not change: one capture, two replays"
+    run([6])
+    if captured and _calls(ctx, "extract.graph_capture_failed") == failed0:
+        assert _calls(ctx, "extract.graph_captures") == c0 + 2, "a batch of one is another graph"
+    ex.close()
+
+
 def test_device_octree_equals_host_octree(ctx, monkeypatch):
     """k_octree (default) and the host octree (option device_octree=0, taken when the extractor is created) select
     the same keypoints in the same order - and both equal the oracle."""
