@@ -294,10 +294,10 @@ int ft_bow_transform(ft_vocabulary *v, const uint8_t *descriptors, int n, int on
 // ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (src/ORBmatcher.cc:322-524): the matching inside the common
 // nodes on the device (k_search_by_bow), the rotation-consistency filter (:489-521, ComputeThreeMaxima :2210-2251) here on the
 // downloaded assignments - the order inside a histogram bin does not matter to it, only the bins' sizes.
-namespace {
-int checkBowSide(const ft_bow_side *s, const char *who) {
+// (shared with ft_search_by_bow_keyframes, bow_kf_search.cpp, which passes its own name as `fn`)
+int checkBowSide(const ft_bow_side *s, const char *who, const char *fn) {
     auto bad = [&](const char *what) {
-        ft_set_error(std::string("ft_search_by_bow: ") + who + ": " + what);
+        ft_set_error(std::string(fn) + ": " + who + ": " + what);
         return FT_ERR_INVALID;
     };
     if (s->n < 0 || s->n >= (1 << 20) || s->n_nodes < 0) return bad("count out of range");
@@ -316,7 +316,6 @@ int checkBowSide(const ft_bow_side *s, const char *who) {
         if (s->fv_features[e] >= (unsigned)s->n) return bad("feature index out of range");
     return FT_OK;
 }
-}  // namespace
 
 int ft_search_by_bow(ft_context *ctx, const ft_bow_side *kf, const uint8_t *kf_has_point, const ft_bow_side *frame, int frame_nleft,
                      float nn_ratio, int check_orientation, int *matches, int *n_matches) {

@@ -354,6 +354,30 @@ struct FtTriangCall {
 int ft_launch_triang_match(hipStream_t st, const FtTriangCall &T);
 int ft_launch_triang_finish(hipStream_t st, const FtTriangCall &T);
 
+// ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:864-1004; kernels_bow_kf.hip) for keyframe 1 against every
+// neighbour of a call.  One arena as above: records hold byte offsets into it.
+struct FtBowKfSide {
+    int n, nNodes, nLeft, nUn;       // KeyFrame::N, FeatureVector entries, KeyFrame::NLeft, mvKeysUn.size()
+    unsigned nodes, offsets, feats;  // the FeatureVector in CSR form
+    unsigned desc, hasPoint, angles; // n x 32, uint8[n], float[n] (angles only with checkOrientation)
+};
+struct FtBowKfJob {  // one neighbour
+    FtBowKfSide K2;
+    unsigned matches;  // int[K1.n], -1 from the host's fill
+    unsigned claimed;  // int[K2.n], 0 from the host's fill: vbMatched2 of the lists too long for the registers
+};
+struct FtBowKfCall {
+    uint8_t *arena;
+    FtBowKfSide K1;
+    unsigned jobs;      // FtBowKfJob[nNeighbours]
+    unsigned nMatches;  // int[nNeighbours]
+    int nNeighbours, checkOrientation;
+    float nnRatio;
+};
+// the two launches of a call, in this order
+int ft_launch_bow_kf_match(hipStream_t st, const FtBowKfCall &T);
+int ft_launch_bow_kf_finish(hipStream_t st, const FtBowKfCall &T);
+
 // ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1247-1437,
 // :1439-1554; kernels_fuse.hip) for one list of map points against every target of a call.  A TARGET is one (keyframe, camera):
 // the host hands the searched camera's keypoints over as a one-camera device frame (F.Nleft == -1; the right camera of a

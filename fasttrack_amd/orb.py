@@ -1037,6 +1037,35 @@ def search_by_bow(ctx: Context, kf: BowSide, kf_has_point, frame: BowSide, frame
     return dict(matches=m[:frame.c.n], n=n.value)
 
 
+class BowKeyFrame:
+    """What ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) reads of a KeyFrame (ft_bow_keyframe).  side: BowSide (mFeatVec,
+    mDescriptors, the angles of mvKeysUn); has_point[i] = GetMapPoint(i) exists and is not bad; n_left = KeyFrame::NLeft (-1 = one
+    camera); n_un = mvKeysUn.size(), read only when n_left != -1 (None: side.n).  Owns the arrays."""
+
+    def __init__(self, side: BowSide, has_point, n_left=-1, n_un=None):
+        self.side = side
+        self.has_point = np.ascontiguousarray(has_point, np.uint8)
+        assert len(self.has_point) == side.c.n
+        c = _capi.BowKeyFrame()
+        c.side = side.c
+        c.has_point = ptr(self.has_point)
+        c.n_left, c.n_un = int(n_left), int(side.c.n if n_un is None else n_un)
+        self.c = c
+
+
+def search_by_bow_keyframes(ctx: Context, kf1: BowKeyFrame, neighbours, nn_ratio=0.9, check_orientation=True):
+    """ORBmatcher(nn_ratio, check_orientation).SearchByBoW(pKF1, pKF2, vpMatches12) for pKF1 against every keyframe of
+    `neighbours` (BowKeyFrame list) in one call (ft_search_by_bow_keyframes) ->
+    dict(matches12 [J, kf1.n] = feature index of neighbour j whose map point vpMatches12[idx1] receives, or -1; n [J] = nmatches)"""
+    nn, n1 = len(neighbours), kf1.c.side.n
+    K2 = (_capi.BowKeyFrame * max(nn, 1))(*[k.c for k in neighbours])
+    cnt = np.zeros(max(nn, 1), np.int32)
+    mflat = np.full(max(nn * n1, 1), -1, np.int32)
+    check(lib().ft_search_by_bow_keyframes(ctx._h, C.byref(kf1.c), nn, K2, float(nn_ratio), int(bool(check_orientation)), ptr(mflat),
+                                           ptr(cnt)))
+    return dict(matches12=mflat[:nn * n1].reshape(nn, n1), n=cnt[:nn])
+
+
 class TriangKeyFrame:
     """What ORBmatcher::SearchForTriangulation reads of a KeyFrame (ft_triang_keyframe).  keys: KP_DTYPE records (mvKeysUn, or
     mvKeys followed by mvKeysRight when n_left != -1); fv_*: mFeatVec as Vocabulary.transform returns it; has_point[i] =

@@ -717,6 +717,40 @@ FT_API int ft_search_by_bow(ft_context *ctx, const ft_bow_side *kf, const uint8_
                             int frame_nleft, float nn_ratio, int check_orientation, int *matches, int *n_matches);
 
 /* ----------------------------------------------------------------------------------------------
+ * ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint*> &vpMatches12) (src/ORBmatcher.cc:864-1004),
+ * the first step of LoopClosing::DetectCommonRegionsFromBoW (src/LoopClosing.cc:657-668), for keyframe 1 against ALL the
+ * keyframes of a call: the calls of the reference's loop share keyframe 1 and are independent of each other.
+ * For every vocabulary node the two FeatureVectors share, keyframe 1's features are taken in the order of the node's list.  A
+ * feature idx1 is skipped when n_left != -1 && idx1 >= n_un (:899: mvKeysUn of a two-camera keyframe holds the left keypoints
+ * only, so a FeatureVector may list right-camera features and they are skipped) or when has_point[idx1] == 0 (no map point, or
+ * a bad one, :903-907).  A candidate idx2 of the same node in keyframe 2 is skipped under the same two conditions (:919,
+ * :925-929) and when an earlier feature of keyframe 1 has taken it (vbMatched2); a skipped candidate is neither best nor second
+ * best.  bestDist1 / bestIdx2 / bestDist2 follow a strict < in scan order (:935-944): the best candidate is the first of the
+ * node's list with the smallest distance, bestDist2 stays 256 with one candidate.  Accepted when bestDist1 < TH_LOW - strictly:
+ * 50 is rejected (:947; the KeyFrame, Frame overload above has <=) - and (float)bestDist1 < nn_ratio * (float)bestDist2, one
+ * fp32 product.  Then the rotation histogram of angle1[idx1] - angle2[bestIdx2], ComputeThreeMaxima and the removal (:954-964,
+ * :983-1001).
+ * matches12[k * kf1->side.n + idx1] = the feature index idx2 of keyframe k whose map point vpMatches12[idx1] receives, or -1;
+ * n_matches[k] = the return value.  n_keyframes == 1 is the reference's single call; a keyframe 2 with n == 0, without map
+ * points or without a shared node gives all -1 and 0.
+ * Launches per call: 2 whatever n_keyframes (the walk of every (node, keyframe 2) pair; histogram, removal and counts, a
+ * workgroup per keyframe 2), one copy up, one copy down, one wait; kernel timing names them kernel.bow_kf_match /
+ * kernel.bow_kf_finish.  kf1->side.n == 0 or n_keyframes == 0 returns without a launch.
+ * FT_ERR_INVALID: what ft_search_by_bow rejects in a side (fv_nodes not strictly ascending, an fv_features entry >= n, null
+ * arrays); an fv_features entry listed twice; n_left outside [-1, n]; n_un outside [0, n] when n_left != -1; check_orientation
+ * without angles; null has_point.  n < 2^20 per keyframe; FT_ERR_CAPACITY when one call's keyframes exceed 4 GB.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ft_bow_keyframe {
+    ft_bow_side side;          /* n = KeyFrame::N, mFeatVec as CSR, mDescriptors, angles[n] (cv::KeyPoint::angle of mvKeysUn; entries >= n_un are not read) */
+    const uint8_t *has_point;  /* [n] GetMapPoint(i) != NULL && !isBad() */
+    int n_left;                /* KeyFrame::NLeft, -1 = one camera */
+    int n_un;                  /* mvKeysUn.size(); read only when n_left != -1 */
+} ft_bow_keyframe;
+FT_API int ft_search_by_bow_keyframes(ft_context *ctx, const ft_bow_keyframe *kf1, int n_keyframes,
+                                      const ft_bow_keyframe *kf2 /* [n_keyframes] */, float nn_ratio, int check_orientation,
+                                      int *matches12 /* n_keyframes x kf1->side.n */, int *n_matches /* [n_keyframes] */);
+
+/* ----------------------------------------------------------------------------------------------
  * ORBmatcher::SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, vMatchedPairs, bOnlyStereo, bCoarse)
  * (src/ORBmatcher.cc:1006-1245), the matcher of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:388-466), for keyframe 1
  * against ALL the neighbours that passed the caller's baseline filter in one call: the calls of the reference's neighbour loop

@@ -527,6 +527,35 @@ private:
     ft_vocabulary *h_ = nullptr;
 };
 
+namespace detail {
+// a std::map FeatureVector in the CSR form the C ABI takes, and the ft_bow_side over it
+struct BowCsr {
+    std::vector<unsigned> nodes, feats;
+    std::vector<int> offs;
+};
+inline BowCsr flattenFeatVec(const ORBVocabulary::FeatureVector &fv) {
+    BowCsr c;
+    c.offs.push_back(0);
+    for (const auto &e : fv) {
+        c.nodes.push_back(e.first);
+        c.feats.insert(c.feats.end(), e.second.begin(), e.second.end());
+        c.offs.push_back((int)c.feats.size());
+    }
+    return c;
+}
+inline ft_bow_side bowSide(const BowCsr &c, int n, const uint8_t *d, const float *a) {
+    ft_bow_side s;
+    s.n = n;
+    s.n_nodes = (int)c.nodes.size();
+    s.fv_nodes = c.nodes.data();
+    s.fv_offsets = c.offs.data();
+    s.fv_features = c.feats.data();
+    s.descriptors = d;
+    s.angles = a;
+    return s;
+}
+}  // namespace detail
+
 // ORBmatcher::SearchByBoW(KeyFrame *pKF, Frame &F, vector<MapPoint*> &vpMapPointMatches) (src/ORBmatcher.cc:322-524) on the
 // std::map FeatureVectors of ORBVocabulary::transform.  kfHasPoint[i] = vpMapPointsKF[i] && !vpMapPointsKF[i]->isBad();
 // kfAngles / fAngles = cv::KeyPoint::angle per feature (right-camera features after the left ones, as the reference indexes
@@ -536,38 +565,53 @@ inline int SearchByBoW(Context &ctx, const ORBVocabulary::FeatureVector &kfFeatV
                        const std::vector<uint8_t> &kfHasPoint, const float *kfAngles, const ORBVocabulary::FeatureVector &fFeatVec,
                        const uint8_t *fDescriptors, int fN, const float *fAngles, int fNleft, float nnRatio, bool checkOrientation,
                        std::vector<int> &matches) {
-    struct Csr {
-        std::vector<unsigned> nodes, feats;
-        std::vector<int> offs;
-    };
-    auto flatten = [](const ORBVocabulary::FeatureVector &fv) {
-        Csr c;
-        c.offs.push_back(0);
-        for (const auto &e : fv) {
-            c.nodes.push_back(e.first);
-            c.feats.insert(c.feats.end(), e.second.begin(), e.second.end());
-            c.offs.push_back((int)c.feats.size());
-        }
-        return c;
-    };
-    const Csr k = flatten(kfFeatVec), f = flatten(fFeatVec);
-    auto side = [](const Csr &c, int n, const uint8_t *d, const float *a) {
-        ft_bow_side s;
-        s.n = n;
-        s.n_nodes = (int)c.nodes.size();
-        s.fv_nodes = c.nodes.data();
-        s.fv_offsets = c.offs.data();
-        s.fv_features = c.feats.data();
-        s.descriptors = d;
-        s.angles = a;
-        return s;
-    };
-    const ft_bow_side K = side(k, kfN, kfDescriptors, kfAngles), F = side(f, fN, fDescriptors, fAngles);
+    const detail::BowCsr k = detail::flattenFeatVec(kfFeatVec), f = detail::flattenFeatVec(fFeatVec);
+    const ft_bow_side K = detail::bowSide(k, kfN, kfDescriptors, kfAngles), F = detail::bowSide(f, fN, fDescriptors, fAngles);
     matches.assign(fN > 0 ? fN : 1, -1);
     int nm = 0;
     check(ft_search_by_bow(ctx.handle(), &K, kfHasPoint.data(), &F, fNleft, nnRatio, checkOrientation ? 1 : 0, matches.data(), &nm));
     matches.resize(fN > 0 ? fN : 0);
     return nm;
+}
+
+// What ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12) reads of a KeyFrame: mFeatVec, mDescriptors (N rows),
+// hasPoint[i] = GetMapPoint(i) && !GetMapPoint(i)->isBad(), angles = cv::KeyPoint::angle of mvKeysUn (N entries; those from nUn on
+// are not read), NLeft and nUn = mvKeysUn.size() (read only when NLeft != -1).
+struct BowKeyFrame {
+    const ORBVocabulary::FeatureVector *mFeatVec = nullptr;
+    const uint8_t *mDescriptors = nullptr;
+    int N = 0;
+    const uint8_t *hasPoint = nullptr;
+    const float *angles = nullptr;
+    int NLeft = -1, nUn = 0;
+};
+// ORBmatcher(nnRatio, checkOrientation).SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:864-1004) for pKF1 against every
+// keyframe of kf2s in one call (ft_search_by_bow_keyframes; LoopClosing::DetectCommonRegionsFromBoW, src/LoopClosing.cc:657-668).
+// vvMatches12[k][idx1] = index into kf2s[k]'s GetMapPointMatches() or -1:
+// `vpMatches12[idx1] = m < 0 ? nullptr : vpMapPoints2[m]`.  Returns nmatches per keyframe.
+inline std::vector<int> SearchByBoW(Context &ctx, const BowKeyFrame &kf1, const std::vector<BowKeyFrame> &kf2s, float nnRatio,
+                                    bool checkOrientation, std::vector<std::vector<int>> &vvMatches12) {
+    const size_t nn = kf2s.size(), n1 = kf1.N > 0 ? (size_t)kf1.N : 0;
+    std::vector<detail::BowCsr> csr(nn + 1);
+    auto record = [&](const BowKeyFrame &k, detail::BowCsr &c) {
+        if (!k.mFeatVec) throw std::invalid_argument("SearchByBoW: a keyframe without mFeatVec");
+        c = detail::flattenFeatVec(*k.mFeatVec);
+        ft_bow_keyframe r;
+        r.side = detail::bowSide(c, k.N, k.mDescriptors, k.angles);
+        r.has_point = k.hasPoint;
+        r.n_left = k.NLeft;
+        r.n_un = k.nUn;
+        return r;
+    };
+    const ft_bow_keyframe K1 = record(kf1, csr[nn]);
+    std::vector<ft_bow_keyframe> K2(nn);
+    for (size_t k = 0; k < nn; k++) K2[k] = record(kf2s[k], csr[k]);
+    std::vector<int> flat(nn * n1 + 1, -1), nmatches(nn + 1, 0);
+    check(ft_search_by_bow_keyframes(ctx.handle(), &K1, (int)nn, K2.data(), nnRatio, checkOrientation ? 1 : 0, flat.data(), nmatches.data()));
+    vvMatches12.assign(nn, {});
+    for (size_t k = 0; k < nn; k++) vvMatches12[k].assign(flat.begin() + k * n1, flat.begin() + (k + 1) * n1);
+    nmatches.resize(nn);
+    return nmatches;
 }
 
 // ORBmatcher(0.6, mbCheckOrientation).SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse)
