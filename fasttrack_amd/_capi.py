@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("FT_LIB") or os.path.join(_PKG, "libfasttrack_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "fasttrack_amd.h")
 
 FT_OK, FT_ERR_INVALID, FT_ERR_NO_DEVICE, FT_ERR_HIP, FT_ERR_CAPACITY, FT_ERR_EMPTY = 0, -1, -2, -3, -4, -5
+DISTINCT_MAX_OBSERVATIONS = 1024  # FT_DISTINCT_MAX_OBSERVATIONS: the longest list of ft_distinctive_descriptors
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4"), ("class_id", "<i4")])
@@ -279,6 +280,7 @@ def lib() -> C.CDLL:
     L.ft_search_for_triangulation.argtypes = [vp, C.POINTER(TriangKeyFrame), i, C.POINTER(TriangKeyFrame), C.POINTER(TriangPair), i, i, i, vp, vp, vp]
     L.ft_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseTarget), vp, vp, vp, vp]
     L.ft_search_keyframe_sim3.argtypes = [vp, C.POINTER(FrameView), i, C.POINTER(Sim3Job)]
+    L.ft_distinctive_descriptors.argtypes = [vp, i, vp, vp, vp, vp, vp]
     L.ft_selftest_libm.argtypes = [vp, i, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_ulonglong),
                                    C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]
     L.ft_octree_distribute.argtypes = [vp, i, i, i, i, i, i, vp, i, ip]

@@ -378,6 +378,25 @@ struct FtBowKfCall {
 int ft_launch_bow_kf_match(hipStream_t st, const FtBowKfCall &T);
 int ft_launch_bow_kf_finish(hipStream_t st, const FtBowKfCall &T);
 
+// MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403; kernels_distinct.hip) for every map point of a call.  One arena
+// as above.  The host bins the points with a non-empty list by list length into four job lists, one behind the other in `jobs`:
+// N <= 8, N <= 16 (both served by k_distinct_short), N <= 64 (k_distinct_wave), N <= FT_DISTINCT_MAX_OBSERVATIONS
+// (k_distinct_block).  A job is the point's index; its list is descriptor rows [offsets[p], offsets[p + 1]).
+struct FtDistinctCall {
+    uint8_t *arena;
+    unsigned offsets;     // int[nPoints + 1]: obs_offsets
+    unsigned desc;        // offsets[nPoints] x 32 bytes
+    unsigned jobs;        // int[n8 + n16 + nWave + nBlock]
+    unsigned bestIdx;     // int[nPoints], -1 from the host's fill
+    unsigned bestMedian;  // int[nPoints], -1 from the host's fill
+    unsigned outDesc;     // nPoints x 32 bytes; the rows of points with an empty list are never written
+    int n8, n16, nWave, nBlock;
+};
+// the launches of a call; a class without a job is not launched
+int ft_launch_distinct_short(hipStream_t st, const FtDistinctCall &T);
+int ft_launch_distinct_wave(hipStream_t st, const FtDistinctCall &T);
+int ft_launch_distinct_block(hipStream_t st, const FtDistinctCall &T);
+
 // ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1247-1437,
 // :1439-1554; kernels_fuse.hip) for one list of map points against every target of a call.  A TARGET is one (keyframe, camera):
 // the host hands the searched camera's keypoints over as a one-camera device frame (F.Nleft == -1; the right camera of a

@@ -132,6 +132,27 @@ class Context:
         self._pinned = getattr(self, "_pinned", []) + [p]
         return arr
 
+    def distinctive_descriptors(self, offsets, descriptors, out_descriptors=None, want_median=True, want_descriptors=True):
+        """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) for every map point of a call
+        (ft_distinctive_descriptors).  Point p owns descriptors[offsets[p]:offsets[p + 1]] ([total, 32] uint8): vDescriptors in the
+        reference's order.  -> (best_index [P] = BestIdx, best_median [P] = BestMedian, descriptors [P, 32] = vDescriptors[BestIdx]);
+        a point with an empty list gives -1, -1 and leaves its row as `out_descriptors` passed it (zeros without one).
+        want_median / want_descriptors False: that output is not asked for (NULL) and comes back as None."""
+        offsets = np.ascontiguousarray(offsets, np.int32)
+        assert offsets.ndim == 1 and len(offsets) >= 1
+        n = len(offsets) - 1
+        descriptors = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        assert n == 0 or len(descriptors) >= offsets[-1]
+        idx = np.zeros(max(n, 1), np.int32)
+        med = np.zeros(max(n, 1), np.int32) if want_median else None
+        out = None
+        if want_descriptors:
+            out = np.zeros((max(n, 1), 32), np.uint8) if out_descriptors is None else out_descriptors
+            assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= 32 * n
+        check(lib().ft_distinctive_descriptors(self._h, n, ptr(offsets), ptr(descriptors) if len(descriptors) else None, ptr(idx),
+                                               ptr(med), ptr(out)))
+        return idx[:n], None if med is None else med[:n], None if out is None else out.reshape(-1, 32)[:n]
+
     # frames resident in HBM
     def to_device(self, arr: np.ndarray) -> "DeviceBuffer":
         arr = np.ascontiguousarray(arr)

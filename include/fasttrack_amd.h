@@ -922,6 +922,44 @@ typedef struct ft_sim3_job {
 } ft_sim3_job;
 FT_API int ft_search_keyframe_sim3(ft_context *ctx, const ft_frame_view *kf, int n_jobs, ft_sim3_job *jobs /* [n_jobs] */);
 
+/* ----------------------------------------------------------------------------------------------
+ * MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) for n_points map points in one call: the producer of the
+ * representative descriptor (pMP->GetDescriptor()) every matcher above reads.  The reference calls it in loops over independent
+ * points - every map point of a new keyframe (LocalMapping::ProcessNewKeyFrame, src/LocalMapping.cc:312-323), the same points
+ * again behind the two Fuse calls of SearchInNeighbors (:806-816), every triangulated point (:704), and the loop-closing and
+ * map-creation sites (src/LoopClosing.cc:1130, src/Tracking.cc:2447, 2468, 2616, 3442) - so one call for all of them computes
+ * what the loop does.
+ * Point p owns descriptors[obs_offsets[p] .. obs_offsets[p + 1]): vDescriptors in the caller's order, i.e. the rows the loop at
+ * :348-363 pushes - over the observation map, keyframes with isBad() skipped (:352), the left index first (:356-358), then the
+ * right index (:359-361).  The caller gathers them: the map bookkeeping stays with the caller, as for ft_fuse_search.
+ * With N the length of the list, d(i, j) = ORBmatcher::DescriptorDistance (:377) and row i = d(i, 0 .. N - 1), the 0 of the
+ * diagonal included (:374):
+ *   median(i)  = the element at index (size_t)(0.5 * (N - 1)) = (N - 1) / 2 of the ascending-sorted row (:388-390): the LOWER
+ *                median of an even N;
+ *   BestIdx    = the first i with the smallest median: it starts at 0 (:385) and the compare is a strict < (:392);
+ *   best_index[p] = BestIdx, best_median[p] = BestMedian (:394-395), out_descriptors[p] = vDescriptors[BestIdx] (:401).
+ * N == 0: the reference returns at :365 (or at :343) without touching mDescriptor; here best_index[p] = -1, best_median[p] = -1
+ * and the 32 bytes of out_descriptors[p] stay as the caller passed them.
+ * A distance reaches 256 (a descriptor and its complement); no step holds a distance in a byte.
+ * Per-point cap: a list holds at most FT_DISTINCT_MAX_OBSERVATIONS (1 024) descriptors.  (The reference keeps float
+ * Distances[N][N] on the stack, :371, and dies near N = 1 400 under the default 8 MB stack.)
+ * Launches per call: at most 3, whatever n_points - one per length class that occurs (N <= 16: several points per wave; N <= 64:
+ * a wave per point; longer: a workgroup per point), one copy up, one copy down, one wait; kernel timing names them
+ * kernel.distinct_short / kernel.distinct_wave / kernel.distinct_block; statistics distinctive_descriptors.total,
+ * distinctive_descriptors.launches.  n_points == 0 or every list empty: no launch (best_index / best_median are still filled
+ * with -1).  There is no CPU path.
+ * FT_ERR_INVALID: null ctx, obs_offsets or best_index; descriptors null while obs_offsets[n_points] > 0; n_points < 0;
+ * obs_offsets[0] != 0 or a decreasing offset.  FT_ERR_CAPACITY, ft_last_error() naming the point: a list longer than the cap; a
+ * call whose arena (the descriptors, 48 bytes per point) would pass 4 GB.  No output is written on an error, and descriptors is
+ * not read before every offset has been checked.
+ * ---------------------------------------------------------------------------------------------- */
+#define FT_DISTINCT_MAX_OBSERVATIONS 1024
+FT_API int ft_distinctive_descriptors(ft_context *ctx, int n_points,
+                                      const int *obs_offsets /* [n_points + 1], obs_offsets[0] == 0, non-decreasing */,
+                                      const uint8_t *descriptors /* obs_offsets[n_points] x 32 bytes, host */,
+                                      int *best_index /* [n_points] */, int *best_median /* [n_points] or NULL */,
+                                      uint8_t *out_descriptors /* n_points x 32 bytes or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 // setGPURunMode flags of the reference have no equivalent.
 #pragma once
 
+#include <array>
 #include <cstring>
 #include <map>
 #include <stdexcept>
@@ -715,6 +716,34 @@ inline int SearchByProjection(Context &ctx, const ft_frame_view &pKF, const Sim3
 // candidates of DetectCommonRegionsFromBoW (the jobs' matched / point_keypoint / stage / n_matches are written in place).
 inline void SearchByProjection(Context &ctx, const ft_frame_view &pKF, std::vector<ft_sim3_job> &vJobs) {
     check(ft_search_keyframe_sim3(ctx.handle(), &pKF, (int)vJobs.size(), vJobs.data()));
+}
+
+// MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) for every map point of a loop in one call
+// (ft_distinctive_descriptors): the loops of LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:312-323), SearchInNeighbors
+// (:806-816) and CreateNewMapPoints (:704).  vvDescriptors[p] = the point's vDescriptors as row pointers, in the order the loop at
+// :348-363 pushes them (`pKF->mDescriptors.ptr(leftIndex)`, then `ptr(rightIndex)`, bad keyframes skipped); a list holds at most
+// FT_DISTINCT_MAX_OBSERVATIONS rows.  mDescriptors[p] receives vDescriptors[BestIdx] (:401); the entry of a point with an empty list
+// is left as it is (the reference returns at :365) - the vector is resized to the number of points, its entries are kept.
+// Returns BestIdx per point (-1 for an empty list); bestMedian, when given, BestMedian (-1).
+typedef std::array<uint8_t, 32> Descriptor256;
+inline std::vector<int> ComputeDistinctiveDescriptors(Context &ctx, const std::vector<std::vector<const uint8_t *>> &vvDescriptors,
+                                                      std::vector<Descriptor256> &mDescriptors, std::vector<int> *bestMedian = nullptr) {
+    const size_t np = vvDescriptors.size();
+    std::vector<int> offsets(np + 1, 0);
+    for (size_t p = 0; p < np; p++) offsets[p + 1] = offsets[p] + (int)vvDescriptors[p].size();
+    std::vector<uint8_t> rows((size_t)offsets[np] * 32 + 1);
+    size_t r = 0;
+    for (const std::vector<const uint8_t *> &v : vvDescriptors)
+        for (const uint8_t *d : v) std::memcpy(rows.data() + 32 * r++, d, 32);
+    mDescriptors.resize(np);
+    std::vector<int> bestIdx(np + 1, -1);
+    if (bestMedian) bestMedian->assign(np + 1, -1);
+    check(ft_distinctive_descriptors(ctx.handle(), (int)np, offsets.data(), rows.data(), bestIdx.data(),
+                                     bestMedian ? bestMedian->data() : nullptr,
+                                     np ? reinterpret_cast<uint8_t *>(mDescriptors.data()) : nullptr));
+    bestIdx.resize(np);
+    if (bestMedian) bestMedian->resize(np);
+    return bestIdx;
 }
 
 }  // namespace fasttrack
