@@ -11,7 +11,7 @@
 #include <sstream>
 #include <vector>
 
-#include "ft_host.h"
+#include "search_host.h"
 
 struct ft_vocabulary {
     ft_context *ctx = nullptr;
@@ -20,31 +20,25 @@ struct ft_vocabulary {
     unsigned *d_childList = nullptr, *d_wordId = nullptr;
     uint8_t *d_desc = nullptr;
     double *d_weight = nullptr;
-    // per-call scratch (grow only; calls on one vocabulary are serialised by the mutex)
+    // per-call arena and its pinned mirror (grow only, together; calls on one vocabulary are serialised by the mutex)
     std::mutex mutex;
-    uint8_t *d_in = nullptr;
-    unsigned *d_word = nullptr, *d_node = nullptr;
-    double *d_w = nullptr;
-    unsigned *h_word = nullptr, *h_node = nullptr;
-    double *h_w = nullptr;
-    int cap = 0;
+    uint8_t *d_arena = nullptr, *h_arena = nullptr;
+    int cap = 0;  // features
 };
 
 namespace {
 
+// the arena of a transform of n features: descriptors | word | node | weight (64-byte aligned each: the doubles are aligned)
+struct BowLayout {
+    Arena a;
+    size_t desc, word, node, weight, end;  // (taken in this order)
+    explicit BowLayout(size_t n) : desc(a.take(32 * n)), word(a.take(4 * n)), node(a.take(4 * n)), weight(a.take(8 * n)), end(a.off) {}
+};
+
 void freeScratch(ft_vocabulary *v) {
-    hipFree(v->d_in);
-    hipFree(v->d_word);
-    hipFree(v->d_node);
-    hipFree(v->d_w);
-    hipHostFree(v->h_word);
-    hipHostFree(v->h_node);
-    hipHostFree(v->h_w);
-    v->d_in = nullptr;
-    v->d_word = v->d_node = nullptr;
-    v->d_w = nullptr;
-    v->h_word = v->h_node = nullptr;
-    v->h_w = nullptr;
+    hipFree(v->d_arena);
+    hipHostFree(v->h_arena);
+    v->d_arena = v->h_arena = nullptr;
     v->cap = 0;
 }
 
@@ -52,13 +46,8 @@ int ensureScratch(ft_vocabulary *v, int n) {
     if (n <= v->cap) return FT_OK;
     freeScratch(v);
     const int want = n + n / 2 + 64;
-    FT_HIP(hipMalloc((void **)&v->d_in, (size_t)32 * want));
-    FT_HIP(hipMalloc((void **)&v->d_word, sizeof(unsigned) * want));
-    FT_HIP(hipMalloc((void **)&v->d_node, sizeof(unsigned) * want));
-    FT_HIP(hipMalloc((void **)&v->d_w, sizeof(double) * want));
-    FT_HIP(hipHostMalloc((void **)&v->h_word, sizeof(unsigned) * want, hipHostMallocDefault));
-    FT_HIP(hipHostMalloc((void **)&v->h_node, sizeof(unsigned) * want, hipHostMallocDefault));
-    FT_HIP(hipHostMalloc((void **)&v->h_w, sizeof(double) * want, hipHostMallocDefault));
+    FT_HIP(hipMalloc((void **)&v->d_arena, BowLayout(want).end));
+    FT_HIP(hipHostMalloc((void **)&v->h_arena, BowLayout(want).end, hipHostMallocDefault));
     v->cap = want;
     return FT_OK;
 }
@@ -199,27 +188,32 @@ int ft_bow_transform(ft_vocabulary *v, const uint8_t *descriptors, int n, int on
     rc = ensureScratch(v, n);
     if (rc != FT_OK) return rc;
     hipStream_t st = v->ctx->stream;
-    const uint8_t *d_desc = descriptors;
+    const BowLayout A(n);
+    uint8_t *dev = v->d_arena, *pin = v->h_arena;
+    CallEventTimer own;
+    CallScope C{v->ctx, st, dev, pin, own.evt};
+    const uint8_t *d_desc = descriptors;  // resident descriptors are read where they are
     if (!on_device) {
-        FT_HIP(hipMemcpyAsync(v->d_in, descriptors, (size_t)32 * n, hipMemcpyHostToDevice, st));
-        d_desc = v->d_in;
+        memcpy(pin + A.desc, descriptors, (size_t)32 * n);
+        C.up(A.desc, A.desc + (size_t)32 * n);
+        d_desc = dev + A.desc;
     }
-    FtBowTree t;
-    t.childStart = v->d_childStart;
-    t.childList = v->d_childList;
-    t.desc = v->d_desc;
-    t.wordId = v->d_wordId;
-    t.weight = v->d_weight;
-    t.nNodes = v->nNodes;
-    rc = ft_launch_bow_walk(st, t, d_desc, n, v->L - levelsup, v->d_word, v->d_node, v->d_w);
+    const FtBowTree t{v->d_childStart, v->d_childList, v->d_desc, v->d_wordId, v->d_weight, v->nNodes};
+    C.launch(nullptr, [&] {
+        return ft_launch_bow_walk(st, t, d_desc, n, v->L - levelsup, (unsigned *)(dev + A.word), (unsigned *)(dev + A.node),
+                                  (double *)(dev + A.weight));
+    });
+    // three blocks down, not one: at a frame's 1 200 - 2 000 features each stays within the 16 KB up to which the runtime copies with a
+    // kernel instead of a DMA engine, which one block of 16 n bytes does not - 4 us of 55 with resident descriptors (EXPERIMENTS 26)
+    C.downBlock(A.word, A.word + sizeof(unsigned) * (size_t)n);
+    C.downBlock(A.node, A.node + sizeof(unsigned) * (size_t)n);
+    rc = C.down(A.weight, A.weight + sizeof(double) * (size_t)n);
     if (rc != FT_OK) return rc;
-    FT_HIP(hipMemcpyAsync(v->h_word, v->d_word, sizeof(unsigned) * n, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipMemcpyAsync(v->h_node, v->d_node, sizeof(unsigned) * n, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipMemcpyAsync(v->h_w, v->d_w, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
-    if (word_ids) memcpy(word_ids, v->h_word, sizeof(unsigned) * n);
-    if (node_ids) memcpy(node_ids, v->h_node, sizeof(unsigned) * n);
-    if (weights) memcpy(weights, v->h_w, sizeof(double) * n);
+    const unsigned *h_word = (const unsigned *)(pin + A.word), *h_node = (const unsigned *)(pin + A.node);
+    const double *h_w = (const double *)(pin + A.weight);
+    if (word_ids) memcpy(word_ids, h_word, sizeof(unsigned) * n);
+    if (node_ids) memcpy(node_ids, h_node, sizeof(unsigned) * n);
+    if (weights) memcpy(weights, h_w, sizeof(double) * n);
 
     // ---- BowVector (std::map<WordId, WordValue>): features in order, entries in ascending word id ----
     if (bow_ids) {
@@ -227,15 +221,15 @@ int ft_bow_transform(ft_vocabulary *v, const uint8_t *descriptors, int n, int on
         std::vector<std::pair<unsigned, int>> order;
         order.reserve(n);
         for (int i = 0; i < n; i++)
-            if (v->h_w[i] > 0) order.emplace_back(v->h_word[i], i);
+            if (h_w[i] > 0) order.emplace_back(h_word[i], i);
         std::stable_sort(order.begin(), order.end(), [](const std::pair<unsigned, int> &a, const std::pair<unsigned, int> &b) { return a.first < b.first; });
         const bool tf = v->weighting == 0 || v->weighting == 1;  // TF_IDF or TF: addWeight; IDF / BINARY: addIfNotExist
         int m = 0;
         for (size_t p = 0; p < order.size();) {
             size_t q = p;
-            double val = v->h_w[order[p].second];  // the insert of the first feature of this word
+            double val = h_w[order[p].second];  // the insert of the first feature of this word
             for (q = p + 1; q < order.size() && order[q].first == order[p].first; q++)
-                if (tf) val += v->h_w[order[q].second];  // vit->second += v, in feature order
+                if (tf) val += h_w[order[q].second];  // vit->second += v, in feature order
             if (m >= bow_capacity) {
                 ft_set_error("ft_bow_transform: bow_capacity too small");
                 return FT_ERR_CAPACITY;
@@ -268,7 +262,7 @@ int ft_bow_transform(ft_vocabulary *v, const uint8_t *descriptors, int n, int on
         std::vector<std::pair<unsigned, int>> order;
         order.reserve(n);
         for (int i = 0; i < n; i++)
-            if (v->h_w[i] > 0) order.emplace_back(v->h_node[i], i);
+            if (h_w[i] > 0) order.emplace_back(h_node[i], i);
         std::stable_sort(order.begin(), order.end(), [](const std::pair<unsigned, int> &a, const std::pair<unsigned, int> &b) { return a.first < b.first; });
         int m = 0;
         for (size_t p = 0; p < order.size(); p++) {
@@ -317,6 +311,25 @@ int checkBowSide(const ft_bow_side *s, const char *who, const char *fn) {
     return FT_OK;
 }
 
+// one side of ft_search_by_bow in the call's arena, and its device view once it is staged in the arena's pinned mirror
+struct BowSideLayout { size_t nodes, offsets, features, desc; };
+static BowSideLayout layoutBowSide(Arena &a, const ft_bow_side *s) {
+    BowSideLayout L;
+    L.nodes = a.take(sizeof(unsigned) * (size_t)s->n_nodes);
+    L.offsets = a.take(sizeof(int) * ((size_t)s->n_nodes + 1));
+    L.features = a.take(sizeof(unsigned) * (size_t)std::max(s->fv_offsets[s->n_nodes], 1));
+    L.desc = a.take((size_t)32 * s->n);
+    return L;
+}
+static FtBowSide stageBowSide(const ft_bow_side *s, const BowSideLayout &L, uint8_t *pin, uint8_t *dev) {
+    memcpy(pin + L.nodes, s->fv_nodes, sizeof(unsigned) * (size_t)s->n_nodes);
+    memcpy(pin + L.offsets, s->fv_offsets, sizeof(int) * ((size_t)s->n_nodes + 1));
+    memcpy(pin + L.features, s->fv_features, sizeof(unsigned) * (size_t)s->fv_offsets[s->n_nodes]);
+    memcpy(pin + L.desc, s->descriptors, (size_t)32 * s->n);
+    return FtBowSide{s->n, s->n_nodes, (const unsigned *)(dev + L.nodes), (const int *)(dev + L.offsets),
+                     (const unsigned *)(dev + L.features), dev + L.desc};
+}
+
 int ft_search_by_bow(ft_context *ctx, const ft_bow_side *kf, const uint8_t *kf_has_point, const ft_bow_side *frame, int frame_nleft,
                      float nn_ratio, int check_orientation, int *matches, int *n_matches) {
     FT_REQUIRE(ctx && kf && frame && matches, "ft_search_by_bow: null argument");
@@ -334,85 +347,32 @@ int ft_search_by_bow(ft_context *ctx, const ft_bow_side *kf, const uint8_t *kf_h
     rc = ft_set_device(ctx);
     if (rc != FT_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->matchMutex);
-    // one block of the context's scratch: per side nodes | offsets | features | descriptors, then has_point, then matches
-    auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    struct Lay { size_t nodes, offsets, features, desc; };
-    size_t off = 0;
-    auto lay = [&](const ft_bow_side *s) {
-        Lay L;
-        L.nodes = off; off += up64(sizeof(unsigned) * (size_t)s->n_nodes);
-        L.offsets = off; off += up64(sizeof(int) * ((size_t)s->n_nodes + 1));
-        L.features = off; off += up64(sizeof(unsigned) * (size_t)std::max(s->fv_offsets[s->n_nodes], 1));
-        L.desc = off; off += up64((size_t)32 * s->n);
-        return L;
-    };
-    const Lay lk_ = lay(kf), lf = lay(frame);
-    const size_t oHas = off; off += up64((size_t)kf->n);
-    const size_t oMatches = off; off += up64(sizeof(int) * (size_t)N);
-    rc = ft_ensure_scratch(ctx, off, off);
+    // one block of the context's scratch: per side nodes | offsets | features | descriptors, then has_point, then matches (-1)
+    Arena a;
+    const BowSideLayout Lk = layoutBowSide(a, kf), Lf = layoutBowSide(a, frame);
+    const size_t oHas = a.take((size_t)kf->n);
+    const size_t oMatches = a.take(sizeof(int) * (size_t)N);
+    rc = ft_ensure_scratch(ctx, a.off, a.off);
     if (rc != FT_OK) return rc;
     uint8_t *dev = (uint8_t *)ctx->scratchDev, *pin = (uint8_t *)ctx->scratchPin;
     hipStream_t st = ctx->stream;
-    auto fill = [&](const ft_bow_side *s, const Lay &L) {
-        memcpy(pin + L.nodes, s->fv_nodes, sizeof(unsigned) * (size_t)s->n_nodes);
-        memcpy(pin + L.offsets, s->fv_offsets, sizeof(int) * ((size_t)s->n_nodes + 1));
-        memcpy(pin + L.features, s->fv_features, sizeof(unsigned) * (size_t)s->fv_offsets[s->n_nodes]);
-        memcpy(pin + L.desc, s->descriptors, (size_t)32 * s->n);
-    };
-    fill(kf, lk_);
-    fill(frame, lf);
+    const FtBowSide Dk = stageBowSide(kf, Lk, pin, dev), Df = stageBowSide(frame, Lf, pin, dev);
     memcpy(pin + oHas, kf_has_point, (size_t)kf->n);
     memset(pin + oMatches, 0xff, sizeof(int) * (size_t)N);
-    FT_HIP(hipMemcpyAsync(dev, pin, off, hipMemcpyHostToDevice, st));  // one copy: the block is contiguous
-    auto side = [&](const ft_bow_side *s, const Lay &L) {
-        FtBowSide D;
-        D.n = s->n;
-        D.nNodes = s->n_nodes;
-        D.nodes = (const unsigned *)(dev + L.nodes);
-        D.offsets = (const int *)(dev + L.offsets);
-        D.features = (const unsigned *)(dev + L.features);
-        D.desc = dev + L.desc;
-        return D;
-    };
-    rc = ft_launch_search_by_bow(st, side(kf, lk_), dev + oHas, side(frame, lf), frame_nleft, nn_ratio, (int *)(dev + oMatches));
+    CallEventTimer own;
+    CallScope C{ctx, st, dev, pin, own.evt};
+    C.up(0, a.off);  // one copy: the block is contiguous
+    C.launch(nullptr, [&] { return ft_launch_search_by_bow(st, Dk, dev + oHas, Df, frame_nleft, nn_ratio, (int *)(dev + oMatches)); });
+    rc = C.down(oMatches, oMatches + sizeof(int) * (size_t)N);
     if (rc != FT_OK) return rc;
-    FT_HIP(hipMemcpyAsync(pin + oMatches, dev + oMatches, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
     memcpy(matches, pin + oMatches, sizeof(int) * (size_t)N);
     int nm = 0;
     for (int i = 0; i < N; i++) nm += matches[i] >= 0;
     if (check_orientation) {
-        std::vector<int> rotHist[FT_HISTO_LENGTH];
-        const float factor = 1.0f / FT_HISTO_LENGTH;
-        for (int i = 0; i < N; i++) {
-            if (matches[i] < 0) continue;
-            float rot = kf->angles[matches[i]] - frame->angles[i];
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)std::round(rot * factor);
-            if (bin == FT_HISTO_LENGTH) bin = 0;
-            if (bin >= 0 && bin < FT_HISTO_LENGTH) rotHist[bin].push_back(i);  // the reference asserts
-        }
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < FT_HISTO_LENGTH; i++) {
-            const int sz = (int)rotHist[i].size();
-            if (sz > max1) {
-                max3 = max2; max2 = max1; max1 = sz;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (sz > max2) {
-                max3 = max2; max2 = sz;
-                ind3 = ind2; ind2 = i;
-            } else if (sz > max3) {
-                max3 = sz; ind3 = i;
-            }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        for (int i = 0; i < FT_HISTO_LENGTH; i++)
-            if (i != ind1 && i != ind2 && i != ind3)
-                for (int idx : rotHist[i]) {
-                    matches[idx] = -1;
-                    nm--;
-                }
+        RotHist hist;
+        for (int i = 0; i < N; i++)
+            if (matches[i] >= 0) hist.add(kf->angles[matches[i]], frame->angles[i], i);
+        hist.forDropped([&](int i) { matches[i] = -1, nm--; });
     }
     if (n_matches) *n_matches = nm;
     return FT_OK;

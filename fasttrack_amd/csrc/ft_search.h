@@ -473,7 +473,7 @@ int ft_launch_sim3_resolve(hipStream_t st, const FtDevFrame &F, void *arena, con
 inline size_t ft_sim3_lds_bytes(int nKeys) { return 4 * (((size_t)nKeys + 31) / 32); }
 
 #ifdef __HIPCC__
-// rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero
+// rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero; host twin of the pair: rot_hist.h
 __device__ __forceinline__ int init_bin(float angle1, float angle2) {
     float rot = __fsub_rn(angle1, angle2);
     if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);

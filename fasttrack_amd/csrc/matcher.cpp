@@ -5,7 +5,7 @@
 #include <cstring>
 #include <memory>
 
-#include "ft_host.h"
+#include "search_host.h"
 
 #define FT_GRAPH_MAX_BATCH 8  // latency mode: batches up to this size are captured as graphs / run paired
 
@@ -634,31 +634,29 @@ int ft_fisheye_match(ft_context *ctx, const uint8_t *descL, int nL, const uint8_
     int rc = ft_set_device(ctx);
     if (rc != FT_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->matchMutex);
-    // layout in the context's grow-only scratch: descL | descR | matches, best, second
-    const size_t oL = 0, oR = (((size_t)32 * nL) + 63) & ~(size_t)63, oOut = oR + ((((size_t)32 * std::max(nR, 1)) + 63) & ~(size_t)63);
-    const size_t total = oOut + sizeof(int) * 3 * (size_t)nL;
-    rc = ft_ensure_scratch(ctx, total, total);
+    // the arena: descL | descR || matches, best, second
+    Arena a;
+    const size_t oL = a.take((size_t)32 * nL), oR = a.take((size_t)32 * std::max(nR, 1));
+    const size_t oOut = a.take(sizeof(int) * 3 * (size_t)nL);
+    rc = ft_ensure_scratch(ctx, a.off, a.off);
     if (rc != FT_OK) return rc;
     uint8_t *dev = (uint8_t *)ctx->scratchDev, *pin = (uint8_t *)ctx->scratchPin;
     int *dOut = (int *)(dev + oOut), *hOut = (int *)(pin + oOut);
     hipStream_t st = ctx->stream;
-    // pageable descriptors go up through the context's pinned scratch (one host memcpy each) instead of being staged and
-    // waited for by the runtime copy by copy; descriptors the caller keeps in pinned memory are read where they are
-    auto up = [&](size_t off, const uint8_t *src, size_t bytes) -> int {
-        const uint8_t *from = src;
-        if (!ft_is_pinned_host_range(src, bytes)) {
-            memcpy(pin + off, src, bytes);
-            from = pin + off;
-        }
-        FT_HIP(hipMemcpyAsync(dev + off, from, bytes, hipMemcpyHostToDevice, st));
-        return FT_OK;
+    CallEventTimer own;
+    CallScope C{ctx, st, dev, pin, own.evt};
+    // pageable descriptors go up through the pinned mirror (one host memcpy each) instead of being staged and waited for by
+    // the runtime copy by copy; descriptors the caller keeps in pinned memory are read where they are
+    auto up = [&](size_t off, const uint8_t *src, size_t bytes) {
+        if (ft_is_pinned_host_range(src, bytes)) return C.upFrom(off, src, bytes);
+        memcpy(pin + off, src, bytes);
+        C.up(off, off + bytes);
     };
-    if ((rc = up(oL, descL, (size_t)32 * nL)) != FT_OK) return rc;
-    if (nR > 0 && (rc = up(oR, descR, (size_t)32 * nR)) != FT_OK) return rc;
-    rc = ft_launch_fisheye(st, dev + oL, nL, dev + oR, nR, dOut, dOut + nL, dOut + 2 * (size_t)nL);
+    up(oL, descL, (size_t)32 * nL);
+    if (nR > 0) up(oR, descR, (size_t)32 * nR);
+    C.launch(nullptr, [&] { return ft_launch_fisheye(st, dev + oL, nL, dev + oR, nR, dOut, dOut + nL, dOut + 2 * (size_t)nL); });
+    rc = C.down(oOut, a.off);
     if (rc != FT_OK) return rc;
-    FT_HIP(hipMemcpyAsync(hOut, dOut, sizeof(int) * 3 * (size_t)nL, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
     memcpy(matches, hOut, sizeof(int) * nL);
     if (best) memcpy(best, hOut + nL, sizeof(int) * nL);
     if (second) memcpy(second, hOut + 2 * (size_t)nL, sizeof(int) * nL);
@@ -687,38 +685,42 @@ int ft_fisheye_stereo(ft_context *ctx, const ft_fisheye_rig *rig, const uint8_t 
     memcpy(G.tlr, rig->tlr, sizeof G.tlr);
     for (int i = 0; i < nlevels; i++) G.sigma2[i] = level_sigma2[i];
     std::lock_guard<std::mutex> lk(ctx->matchMutex);
-    auto up = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    // the arena: descL | descR | keysL | keysR | count (0) || matches, best, second | depth | p3d
+    Arena a;
     const size_t nRa = (size_t)std::max(nR, 1);
-    const size_t oDL = 0, oDR = up((size_t)32 * nL), oKL = oDR + up(32 * nRa), oKR = oKL + up(sizeof(ft_keypoint) * nL),
-                 oOut = oKR + up(sizeof(ft_keypoint) * nRa);
-    // outputs: matches | best | second | count(+pad) | depth | p3d
-    const size_t outInts = 3 * (size_t)nL + 16, outBytes = sizeof(int) * outInts + sizeof(float) * 4 * (size_t)nL;
-    rc = ft_ensure_scratch(ctx, oOut + outBytes, outBytes);
+    const size_t oDL = a.take((size_t)32 * nL), oDR = a.take(32 * nRa), oKL = a.take(sizeof(ft_keypoint) * nL),
+                 oKR = a.take(sizeof(ft_keypoint) * nRa), oCount = a.take(sizeof(int));
+    const size_t inputEnd = a.off;
+    const size_t oM = a.take(sizeof(int) * 3 * (size_t)nL), oOut = a.take(sizeof(float) * 4 * (size_t)nL);
+    rc = ft_ensure_scratch(ctx, a.off, a.off);
     if (rc != FT_OK) return rc;
     uint8_t *dev = (uint8_t *)ctx->scratchDev, *pin = (uint8_t *)ctx->scratchPin;
-    int *dM = (int *)(dev + oOut), *dCount = dM + 3 * (size_t)nL;
-    float *dOut = (float *)(dM + outInts);
+    int *dM = (int *)(dev + oM), *dCount = (int *)(dev + oCount);
+    float *dOut = (float *)(dev + oOut);
     hipStream_t st = ctx->stream;
-    FT_HIP(hipMemcpyAsync(dev + oDL, descL, (size_t)32 * nL, hipMemcpyHostToDevice, st));
-    FT_HIP(hipMemcpyAsync(dev + oKL, keysL, sizeof(ft_keypoint) * nL, hipMemcpyHostToDevice, st));
+    memcpy(pin + oDL, descL, (size_t)32 * nL);
+    memcpy(pin + oKL, keysL, sizeof(ft_keypoint) * nL);
     if (nR > 0) {
-        FT_HIP(hipMemcpyAsync(dev + oDR, descR, (size_t)32 * nR, hipMemcpyHostToDevice, st));
-        FT_HIP(hipMemcpyAsync(dev + oKR, keysR, sizeof(ft_keypoint) * nR, hipMemcpyHostToDevice, st));
+        memcpy(pin + oDR, descR, (size_t)32 * nR);
+        memcpy(pin + oKR, keysR, sizeof(ft_keypoint) * nR);
     }
-    FT_HIP(hipMemsetAsync(dCount, 0, sizeof(int), st));
-    rc = ft_launch_fisheye(st, dev + oDL, nL, dev + oDR, nR, dM, dM + nL, dM + 2 * (size_t)nL);
-    if (rc == FT_OK)
-        rc = ft_launch_fisheye_triangulate(st, G, (const ft_keypoint *)(dev + oKL), nL, (const ft_keypoint *)(dev + oKR), dM, dOut,
-                                           dOut + nL, dCount);
+    memset(pin + oCount, 0, sizeof(int));
+    CallEventTimer own;
+    CallScope C{ctx, st, dev, pin, own.evt};
+    C.up(0, inputEnd);
+    C.launch(nullptr, [&] { return ft_launch_fisheye(st, dev + oDL, nL, dev + oDR, nR, dM, dM + nL, dM + 2 * (size_t)nL); });
+    C.launch(nullptr, [&] {
+        return ft_launch_fisheye_triangulate(st, G, (const ft_keypoint *)(dev + oKL), nL, (const ft_keypoint *)(dev + oKR), dM, dOut,
+                                             dOut + nL, dCount);
+    });
+    rc = C.down(oCount, a.off);
     if (rc != FT_OK) return rc;
-    FT_HIP(hipMemcpyAsync(pin, dev + oOut, outBytes, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
-    const int *hM = (const int *)pin;
-    const float *hOut = (const float *)(hM + outInts);
+    const int *hM = (const int *)(pin + oM);
+    const float *hOut = (const float *)(pin + oOut);
     memcpy(matches, hM, sizeof(int) * nL);
     memcpy(depth, hOut, sizeof(float) * nL);
     memcpy(p3d, hOut + nL, sizeof(float) * 3 * (size_t)nL);
-    if (n_matches) *n_matches = hM[3 * (size_t)nL];
+    if (n_matches) *n_matches = *(const int *)(pin + oCount);
     return FT_OK;
 }
 
@@ -739,18 +741,21 @@ int ft_descriptor_distance(ft_context *ctx, const uint8_t *a, const uint8_t *b, 
     int rc = ft_set_device(ctx);
     if (rc != FT_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->matchMutex);
-    const size_t oA = 0, oB = (((size_t)32 * n) + 63) & ~(size_t)63, oD = 2 * oB;
-    rc = ft_ensure_scratch(ctx, oD + sizeof(int) * (size_t)n, sizeof(int) * (size_t)n);
+    Arena ar;
+    const size_t oA = ar.take((size_t)32 * n), oB = ar.take((size_t)32 * n), oD = ar.take(sizeof(int) * (size_t)n);
+    rc = ft_ensure_scratch(ctx, ar.off, ar.off);
     if (rc != FT_OK) return rc;
-    uint8_t *dev = (uint8_t *)ctx->scratchDev;
+    uint8_t *dev = (uint8_t *)ctx->scratchDev, *pin = (uint8_t *)ctx->scratchPin;
     hipStream_t st = ctx->stream;
-    FT_HIP(hipMemcpyAsync(dev + oA, a, (size_t)32 * n, hipMemcpyHostToDevice, st));
-    FT_HIP(hipMemcpyAsync(dev + oB, b, (size_t)32 * n, hipMemcpyHostToDevice, st));
-    rc = ft_launch_hamming_pairs(st, dev + oA, dev + oB, n, (int *)(dev + oD));
+    memcpy(pin + oA, a, (size_t)32 * n);
+    memcpy(pin + oB, b, (size_t)32 * n);
+    CallEventTimer own;
+    CallScope C{ctx, st, dev, pin, own.evt};
+    C.up(0, oD);
+    C.launch(nullptr, [&] { return ft_launch_hamming_pairs(st, dev + oA, dev + oB, n, (int *)(dev + oD)); });
+    rc = C.down(oD, oD + sizeof(int) * (size_t)n);
     if (rc != FT_OK) return rc;
-    FT_HIP(hipMemcpyAsync(ctx->scratchPin, dev + oD, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
-    memcpy(dist, ctx->scratchPin, sizeof(int) * (size_t)n);
+    memcpy(dist, pin + oD, sizeof(int) * (size_t)n);
     return FT_OK;
 }
 

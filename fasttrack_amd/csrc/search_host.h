@@ -1,5 +1,6 @@
 // Host side of the projection searches, shared by the translation units of the entry-point families (search_view.cpp,
-// tracked_frame.cpp, init_search.cpp, reloc_search.cpp, triang_search.cpp, fuse_search.cpp, sim3_search.cpp, tracked_batch.cpp): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
+// tracked_frame.cpp, init_search.cpp, reloc_search.cpp, triang_search.cpp, fuse_search.cpp, sim3_search.cpp, tracked_batch.cpp; bow.cpp, bow_kf_search.cpp,
+// distinct_desc.cpp and matcher.cpp for the call skeleton at the end: Arena, CallScope): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
 // (reference include/Kernels/KernelController.h:40-46) together with the acceptance loops the reference keeps in the caller
 // (src/ORBmatcher.cc:241-308, 2013-2081).  Windowing, level/box tests and every Hamming distance run on the device
 // (kernels_search*.hip, kernels_resolve.hip, kernels_frame.hip); the host only marshals arrays, drives the fixed-point passes and
@@ -13,6 +14,7 @@
 
 #include "ft_host.h"
 #include "ft_search.h"
+#include "rot_hist.h"
 
 struct Arena {
     size_t off = 0;
@@ -274,14 +276,13 @@ inline int replayLocalWrites(const int *res, int M, const int *observations, int
 }
 
 // Replays the writes of SearchByProjection(CurrentFrame, LastFrame) in last-frame order with the rotation histogram
-// of ORBmatcher.cc:1880-1896, 1942-1957, 1966-1987 and ComputeThreeMaxima (:2210-2251).  curAngle(i) = angle of
+// of ORBmatcher.cc:1880-1896, 1942-1957, 1966-1987 and ComputeThreeMaxima (:2210-2251): rot_hist.h.  curAngle(i) = angle of
 // keypoint i of the current frame (left keypoints, then right).
 template <typename AngleFn>
 inline int replayLastFrameWrites(const int *res, int M, const ft_last_points *L, AngleFn curAngle, bool checkOrientation, int *holder,
                           int *assign) {
     int nm = 0;
-    std::vector<int> rotHist[FT_HISTO_LENGTH];
-    const float factor = 1.0f / FT_HISTO_LENGTH;
+    RotHist hist;
     for (int i = 0; i < M; i++) {
         const int w2[2] = {res[4 * i], res[4 * i + 2]};
         for (int k = 0; k < 2; k++) {
@@ -290,39 +291,10 @@ inline int replayLastFrameWrites(const int *res, int M, const ft_last_points *L,
             holder[kp] = L->observations[i];
             assign[kp] = i;
             nm++;
-            if (checkOrientation) {
-                float rot = L->angle[i] - curAngle(kp);
-                if (rot < 0.0) rot += 360.0f;
-                int bin = (int)std::round(rot * factor);
-                if (bin == FT_HISTO_LENGTH) bin = 0;
-                if (bin >= 0 && bin < FT_HISTO_LENGTH) rotHist[bin].push_back(kp);  // the reference asserts
-            }
+            if (checkOrientation) hist.add(L->angle[i], curAngle(kp), kp);
         }
     }
-    if (checkOrientation) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < FT_HISTO_LENGTH; i++) {
-            const int sz = (int)rotHist[i].size();
-            if (sz > max1) {
-                max3 = max2; max2 = max1; max1 = sz;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (sz > max2) {
-                max3 = max2; max2 = sz;
-                ind3 = ind2; ind2 = i;
-            } else if (sz > max3) {
-                max3 = sz; ind3 = i;
-            }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        for (int i = 0; i < FT_HISTO_LENGTH; i++)
-            if (i != ind1 && i != ind2 && i != ind3)
-                for (int kp : rotHist[i]) {
-                    assign[kp] = -1;
-                    holder[kp] = -1;
-                    nm--;
-                }
-    }
+    hist.forDropped([&](int kp) { assign[kp] = holder[kp] = -1, nm--; });
     return nm;
 }
 
@@ -413,15 +385,6 @@ inline FtFrustumOut devFrustumOut(const FrustumLayout &L, uint8_t *dev) {
     return O;
 }
 
-// D2H of the frustum fields the caller asked for (one contiguous copy of the output block, then scatter)
-inline void unpackFrustum(int M, const FrustumLayout &L, size_t outBegin, uint8_t *pin, const ft_frustum_result *R, int *n_to_match);
-inline int downloadFrustum(hipStream_t st, int M, const FrustumLayout &L, size_t outBegin, size_t outEnd, uint8_t *dev, uint8_t *pin,
-                    const ft_frustum_result *R, int *n_to_match) {
-    FT_HIP(hipMemcpyAsync(pin, dev + outBegin, outEnd - outBegin, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
-    unpackFrustum(M, L, outBegin, pin, R, n_to_match);
-    return FT_OK;
-}
 // the frustum fields of the output block [outBegin, ...) that sits at the start of `pin`
 inline void unpackFrustum(int M, const FrustumLayout &L, size_t outBegin, uint8_t *pin, const ft_frustum_result *R, int *n_to_match) {
     auto at = [&](size_t off) { return pin + (off - outBegin); };
@@ -440,6 +403,14 @@ inline void unpackFrustum(int M, const FrustumLayout &L, size_t outBegin, uint8_
     if (R->proj_yr) memcpy(R->proj_yr, at(L.pyr), 4 * m);
     if (R->depth) memcpy(R->depth, at(L.dep), 4 * m);
     if (R->depth_r) memcpy(R->depth_r, at(L.depR), 4 * m);
+}
+// D2H of the frustum fields the caller asked for (one contiguous copy of the output block, then scatter)
+inline int downloadFrustum(hipStream_t st, int M, const FrustumLayout &L, size_t outBegin, size_t outEnd, uint8_t *dev, uint8_t *pin,
+                    const ft_frustum_result *R, int *n_to_match) {
+    FT_HIP(hipMemcpyAsync(pin, dev + outBegin, outEnd - outBegin, hipMemcpyDeviceToHost, st));
+    FT_HIP(hipStreamSynchronize(st));
+    unpackFrustum(M, L, outBegin, pin, R, n_to_match);
+    return FT_OK;
 }
 
 inline FtPose poseOfMatrix(const float *T) {
@@ -723,7 +694,7 @@ inline int ensureInitArena(ft_tracked_frame *tf, size_t devBytes, size_t pinByte
     return FT_OK;
 }
 
-// ---- a one-shot search (initialisation, relocalisation, triangulation, Fuse, Sim3) ----
+// ---- a one-shot call on an arena and its pinned mirror: the keyframe matchers, bow.cpp, matcher.cpp's fisheye / distance calls, search_view.cpp's queries ----
 // The event timer of a stand-alone call, destroyed with the call's scope.  (FtEventTimer itself has no destructor: extractors,
 // tracked frames and batches keep theirs for their lifetime and destroy it where they free their streams.)
 struct CallEventTimer {
@@ -733,7 +704,7 @@ struct CallEventTimer {
 // What such a call enqueues on the context's stream between its arena `dev` and the arena's pinned mirror `pin` (the context's
 // scratch, or a tracked frame's own arena with the frame's timer): blocks up, launches, one block down - and one wait.  The first
 // failure sticks: what follows is skipped, and down() waits for what was enqueued before the error leaves the entry point (the
-// next call may free the arena).  Every path of an entry point behind its first up() ends in down().
+// next call may free the arena).  Every path of an entry point behind its first up() ends in down() (ft_features_in_area: per phase).
 struct CallScope {
     ft_context *ctx;
     hipStream_t st;
@@ -746,6 +717,10 @@ struct CallScope {
     }
     void up(size_t begin, size_t end) {
         if (rc == FT_OK) hip(hipMemcpyAsync(dev + begin, pin + begin, end - begin, hipMemcpyHostToDevice, st), "hipMemcpyAsync (block up)");
+    }
+    // an input the caller holds in pinned memory goes up from where it is (ft_is_pinned_host_range), not through the mirror
+    void upFrom(size_t begin, const void *src, size_t bytes) {
+        if (rc == FT_OK) hip(hipMemcpyAsync(dev + begin, src, bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync (block up)");
     }
     void zero(size_t begin, size_t end) {
         if (rc == FT_OK) hip(hipMemsetAsync(dev + begin, 0, end - begin, st), "hipMemsetAsync");
@@ -760,10 +735,13 @@ struct CallScope {
         evt.end(tm, st);
         launches++;
     }
-    int down(size_t begin, size_t end) {
+    // a block down without the wait, in front of down(): for outputs that come down cheaper apart than as one block (ft_bow_transform)
+    void downBlock(size_t begin, size_t end) {
         if (rc == FT_OK) hip(hipMemcpyAsync(pin + begin, dev + begin, end - begin, hipMemcpyDeviceToHost, st), "hipMemcpyAsync (block down)");
-        const hipError_t e = hipStreamSynchronize(st);
-        hip(e, "hipStreamSynchronize");
+    }
+    int down(size_t begin, size_t end) {
+        downBlock(begin, end);
+        hip(hipStreamSynchronize(st), "hipStreamSynchronize");
         if (rc == FT_OK) evt.resolve(ctx);
         else evt.recs.clear(), evt.used = 0;
         return rc;

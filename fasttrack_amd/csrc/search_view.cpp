@@ -192,7 +192,7 @@ int ft_features_in_area(ft_context *ctx, const ft_frame_view *F, int nq, const f
     if (rc != FT_OK) return rc;
     uint8_t *pin = (uint8_t *)ctx->scratchPin, *dev = (uint8_t *)ctx->scratchDev;
     hipStream_t st = ctx->stream;
-    auto stageInputs = [&]() -> int {  // the frame and the queries into the pinned scratch and up
+    auto stageInputs = [&] {  // the frame and the queries into the pinned mirror
         stageFrame(F, FL, pin);
         memcpy(pin + oX, x, 4 * Q);
         memcpy(pin + oY, y, 4 * Q);
@@ -200,52 +200,48 @@ int ft_features_in_area(ft_context *ctx, const ft_frame_view *F, int nq, const f
         memcpy(pin + oMin, min_level, 4 * Q);
         memcpy(pin + oMax, max_level, 4 * Q);
         if (right) memcpy(pin + oRight, right, Q);
-        FT_HIP(hipMemcpyAsync(dev, pin, inputBytes, hipMemcpyHostToDevice, st));
-        return FT_OK;
     };
-    if ((rc = stageInputs()) != FT_OK) return rc;
-    FtDevFrame DF = devFrame(F, FL, dev);
     auto launch = [&](const int *offsets, unsigned *keys) {
-        return ft_launch_features_in_area(st, DF, nq, (const float *)(dev + oX), (const float *)(dev + oY),
+        return ft_launch_features_in_area(st, devFrame(F, FL, dev), nq, (const float *)(dev + oX), (const float *)(dev + oY),
                                           (const float *)(dev + oR), (const int *)(dev + oMin), (const int *)(dev + oMax),
                                           right ? dev + oRight : nullptr, offsets, keys, (int *)(dev + oCount));
     };
-    // pass 1 counts the hits of every query, pass 2 writes them at the query's offset (no capacity inside)
-    rc = launch(nullptr, nullptr);
+    CallEventTimer own;
+    // phase 1 counts the hits of every query, phase 2 writes them at the query's offset (no capacity inside)
+    stageInputs();
+    CallScope C1{ctx, st, dev, pin, own.evt};
+    C1.up(0, inputBytes);
+    C1.launch(nullptr, [&] { return launch(nullptr, nullptr); });
+    rc = C1.down(oCount, oCount + 4 * Q);
     if (rc != FT_OK) return rc;
-    std::vector<int> hCount(nq), hOff(nq);
-    FT_HIP(hipMemcpyAsync(hCount.data(), dev + oCount, 4 * Q, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
+    memcpy(counts, pin + oCount, 4 * Q);
     size_t totalHits = 0;
-    for (int q = 0; q < nq; q++) {
-        hOff[q] = (int)totalHits;
-        totalHits += (size_t)hCount[q];
-        counts[q] = hCount[q];
-    }
+    for (int q = 0; q < nq; q++) totalHits += (size_t)counts[q];
     if (totalHits == 0) return FT_OK;
     FT_REQUIRE(totalHits < (1u << 30), "ft_features_in_area: too many hits");
     const size_t oKeys = a.take(4 * totalHits);
-    // growing the scratch buffer reallocates it: the frame and the queries are staged again in that case
-    const void *devBefore = ctx->scratchDev;
-    rc = ft_ensure_scratch(ctx, a.off, std::max(fixedBytes, 4 * totalHits));
+    // growing the scratch reallocates it (nothing is in flight: phase 1 has been waited for, and the counts are the caller's
+    // by now): where the device side moved, the frame and the queries are staged and go up again
+    const size_t devBytesBefore = ctx->scratchDevBytes;
+    rc = ft_ensure_scratch(ctx, a.off, a.off);
     if (rc != FT_OK) return rc;
-    pin = (uint8_t *)ctx->scratchPin;
-    dev = (uint8_t *)ctx->scratchDev;
-    if (ctx->scratchDev != devBefore) {
-        if ((rc = stageInputs()) != FT_OK) return rc;
-        FT_HIP(hipStreamSynchronize(st));
-        DF = devFrame(F, FL, dev);
+    pin = (uint8_t *)ctx->scratchPin, dev = (uint8_t *)ctx->scratchDev;
+    CallScope C2{ctx, st, dev, pin, own.evt};
+    if (ctx->scratchDevBytes != devBytesBefore) {
+        stageInputs();
+        C2.up(0, inputBytes);
     }
-    FT_HIP(hipMemcpyAsync(dev + oOff, hOff.data(), 4 * Q, hipMemcpyHostToDevice, st));
-    rc = launch((const int *)(dev + oOff), (unsigned *)(dev + oKeys));
+    int *hOff = (int *)(pin + oOff);
+    for (int q = 0, at = 0; q < nq; at += counts[q++]) hOff[q] = at;
+    C2.up(oOff, oOff + 4 * Q);
+    C2.launch(nullptr, [&] { return launch((const int *)(dev + oOff), (unsigned *)(dev + oKeys)); });
+    rc = C2.down(oKeys, oKeys + 4 * totalHits);
     if (rc != FT_OK) return rc;
-    unsigned *hKeys = (unsigned *)pin;
-    FT_HIP(hipMemcpyAsync(hKeys, dev + oKeys, 4 * totalHits, hipMemcpyDeviceToHost, st));
-    FT_HIP(hipStreamSynchronize(st));
+    unsigned *hKeys = (unsigned *)(pin + oKeys);
     for (int q = 0; q < nq; q++) {
         unsigned *k = hKeys + hOff[q];
-        std::sort(k, k + hCount[q]);  // (cell column, cell row, index): the order of the nested loops of Frame.cc:718-744
-        const int m = std::min(hCount[q], capacity);
+        std::sort(k, k + counts[q]);  // (cell column, cell row, index): the order of the nested loops of Frame.cc:718-744
+        const int m = std::min(counts[q], capacity);
         for (int i = 0; i < m; i++) indices[(size_t)q * capacity + i] = (int)(k[i] & 0xfffffu);
     }
     return FT_OK;
@@ -273,12 +269,15 @@ int ft_is_in_frustum(ft_context *ctx, const ft_frame_view *F, const ft_frame_pos
     uint8_t *pin = (uint8_t *)ctx->scratchPin, *dev = (uint8_t *)ctx->scratchDev;
     stageFrustum(P, L, pin);
     hipStream_t st = ctx->stream;
-    FT_HIP(hipMemcpyAsync(dev, pin, inputEnd, hipMemcpyHostToDevice, st));
-    const FtDevFrame DF = devFrameConstants(F);
-    rc = ft_launch_frustum(st, DF, frustumPose(F, pose), devMapPoints(P, L, dev), viewing_cos_limit, log_scale_factor, 0, 0.f,
-                           devFrustumOut(L, dev));
-    if (rc != FT_OK) return rc;
-    rc = downloadFrustum(st, P->M, L, inputEnd, a.off, dev, pin, out, n_to_match);
+    CallEventTimer own;
+    CallScope C{ctx, st, dev, pin, own.evt};
+    C.up(0, inputEnd);
+    C.launch(nullptr, [&] {
+        return ft_launch_frustum(st, devFrameConstants(F), frustumPose(F, pose), devMapPoints(P, L, dev), viewing_cos_limit, log_scale_factor,
+                                 0, 0.f, devFrustumOut(L, dev));
+    });
+    rc = C.down(inputEnd, a.off);
+    if (rc == FT_OK) unpackFrustum(P->M, L, inputEnd, pin + inputEnd, out, n_to_match);
     ctx->addStat("is_in_frustum.total", tAll.ms());
     return rc;
 }

@@ -125,6 +125,16 @@ def test_std_sort_replay_matches_libstdcxx(tmp_path):
     assert out.returncode == 0 and "mismatches 0" in out.stdout, out.stdout + out.stderr
 
 
+def test_rot_hist_matches_compute_three_maxima(tmp_path):
+    """rot_hist.h, the host's one rotation-consistency filter (replayLastFrameWrites, ft_search_by_bow), against a restatement of
+    the reference's ComputeThreeMaxima: seeded histograms, the hand cases of the 0.1 thresholds and of ties, the bin edges."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "trh")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(root, "tests", "cpp", "test_rot_hist.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "histograms 6000 mismatches 0" in out.stdout, out.stdout + out.stderr
+
+
 @pytest.mark.parametrize("mode", ["1", "2", "3"])
 def test_path_code_octree_equals_oracle(mode):
     """The path-code formulations the device kernel is built from (octree_paths.h; 1 = node-list replay over
