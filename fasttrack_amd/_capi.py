@@ -18,6 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "fasttrack_amd.h")
 
 FT_OK, FT_ERR_INVALID, FT_ERR_NO_DEVICE, FT_ERR_HIP, FT_ERR_CAPACITY, FT_ERR_EMPTY = 0, -1, -2, -3, -4, -5
 DISTINCT_MAX_OBSERVATIONS = 1024  # FT_DISTINCT_MAX_OBSERVATIONS: the longest list of ft_distinctive_descriptors
+KFDB_MAX_QUERY_WORDS = 4096  # FT_KFDB_MAX_QUERY_WORDS: the longest query of ft_kfdb_score
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4"), ("class_id", "<i4")])
@@ -281,6 +282,17 @@ def lib() -> C.CDLL:
     L.ft_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseTarget), vp, vp, vp, vp]
     L.ft_search_keyframe_sim3.argtypes = [vp, C.POINTER(FrameView), i, C.POINTER(Sim3Job)]
     L.ft_distinctive_descriptors.argtypes = [vp, i, vp, vp, vp, vp, vp]
+    ll = C.c_longlong
+    L.ft_kfdb_create.argtypes = [vp, i, C.POINTER(vp)]
+    L.ft_kfdb_destroy.argtypes = [vp]
+    L.ft_kfdb_add.argtypes = [vp, i, vp, vp, vp, vp]
+    L.ft_kfdb_erase.argtypes = [vp, i, vp]
+    L.ft_kfdb_clear.argtypes = [vp]
+    L.ft_kfdb_size.argtypes = [vp, ip, C.POINTER(ll)]
+    L.ft_kfdb_state.argtypes = [vp, i, i, vp, vp, vp, vp]
+    L.ft_kfdb_score.argtypes = [vp, i, ll, i, vp, vp, i, vp, ip, ip, ip, ip, vp, vp, vp, vp]
+    L.ft_kfdb_select_n_best.argtypes = [vp, ll, i, vp, vp, vp, vp, vp, vp, i, i, vp, i, vp, ip, vp, ip]
+    L.ft_kfdb_select_reloc.argtypes = [vp, ll, i, vp, vp, vp, vp, vp, vp, i, vp, ip]
     L.ft_selftest_libm.argtypes = [vp, i, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_ulonglong),
                                    C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]
     L.ft_octree_distribute.argtypes = [vp, i, i, i, i, i, i, vp, i, ip]

@@ -397,6 +397,46 @@ int ft_launch_distinct_short(hipStream_t st, const FtDistinctCall &T);
 int ft_launch_distinct_wave(hipStream_t st, const FtDistinctCall &T);
 int ft_launch_distinct_block(hipStream_t st, const FtDistinctCall &T);
 
+// KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates up to the scores (src/KeyFrameDatabase.cc:615-666,
+// :741-787; kernels_kfdb.hip) for every stored keyframe of a database.  The BowVectors are resident: ids in one array, values in
+// another, ROW r (a stored keyframe, in handle order) owns words [rowStart[r], rowStart[r] + rowLen[r]); an erased row has
+// rowLen 0.  The per-keyframe members of the query's kind (mnPlaceRecognitionQuery / Words / Score, or the mnReloc* set) are
+// one 16-byte record per row.  The call's arena: the call slot, the query and the connected rows go up; the slot, the records of
+// the scored rows and their doubles come down; `first` stays on the device.
+struct FtKfdbState {
+    long long stamp;  // mn*Query
+    int words;        // mn*Words
+    float score;      // m*Score
+};
+struct FtKfdbRec {  // a scored row, in the order the waves finished (the host orders them by (first, row))
+    int row, first, words;
+    float score;
+};
+struct FtKfdbCall {
+    const unsigned *ids;       // stored word ids
+    const double *vals;        // stored word values
+    const unsigned *rowStart;  // [nRows]
+    const int *rowLen;         // [nRows]
+    FtKfdbState *state;        // [nRows], of the query's kind
+    int nRows;
+    uint8_t *arena;
+    unsigned slot;       // int[16]: [0] listed rows, [1] maxCommonWords, [2] scored rows; zero from the host
+    unsigned qIds;       // unsigned[nQuery] strictly ascending
+    unsigned qVals;      // double[nQuery]
+    unsigned connected;  // int[nConnected] rows, ascending
+    unsigned recs;       // FtKfdbRec[nRows]
+    unsigned raw;        // double[nRows]: the score before the rounding to float, beside recs
+    unsigned first;      // unsigned[nRows]: a listed row's first shared word, FT_KFDB_NOT_LISTED otherwise
+    int nQuery, nConnected;
+    long long queryId;
+};
+#define FT_KFDB_NOT_LISTED 0xffffffffu
+int ft_launch_kfdb_count(hipStream_t st, const FtKfdbCall &T);
+int ft_launch_kfdb_score(hipStream_t st, const FtKfdbCall &T);
+// rows of a database into new storage (growth, compaction): new row r takes the words of old row map[r]
+int ft_launch_kfdb_move(hipStream_t st, const unsigned *oldIds, const double *oldVals, const unsigned *oldStart, const int *map,
+                        unsigned *newIds, double *newVals, const unsigned *newStart, const int *newLen, int nRows);
+
 // ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1247-1437,
 // :1439-1554; kernels_fuse.hip) for one list of map points against every target of a call.  A TARGET is one (keyframe, camera):
 // the host hands the searched camera's keypoints over as a one-camera device frame (F.Nleft == -1; the right camera of a

@@ -554,6 +554,124 @@ class Vocabulary:
                     fv_nodes=fn[:nf.value], fv_offsets=fo[:nf.value + 1], fv_features=ff[:fo[nf.value]])
 
 
+class KeyFrameDatabase:
+    """KeyFrameDatabase (src/KeyFrameDatabase.cc) resident on the device: add / erase / clear and the two queries that have a
+    caller.  A keyframe is known by its HANDLE, the add sequence number.  Per keyframe and query kind the database keeps the
+    reference's stamp, word count and score, and they persist between queries (ft_kfdb_* in include/fasttrack_amd.h)."""
+
+    PLACE, RELOC = 0, 1
+
+    def __init__(self, ctx: Context, scoring=0):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        check(lib().ft_kfdb_create(ctx._h, scoring, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().ft_kfdb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, bow_vectors):
+        """bow_vectors: a list of (ids, values) - the bow_ids / bow_values of Vocabulary.transform.  -> handles [n]"""
+        n = len(bow_vectors)
+        offsets = np.zeros(n + 1, np.int32)
+        for k, (ids, _) in enumerate(bow_vectors):
+            offsets[k + 1] = offsets[k] + len(ids)
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(v[0], np.uint32) for v in bow_vectors] + [np.zeros(0, np.uint32)]))
+        vals = np.ascontiguousarray(np.concatenate([np.asarray(v[1], np.float64) for v in bow_vectors] + [np.zeros(0, np.float64)]))
+        handles = np.zeros(max(n, 1), np.int32)
+        check(lib().ft_kfdb_add(self._h, n, ptr(offsets), ptr(ids) if len(ids) else None, ptr(vals) if len(vals) else None, ptr(handles)))
+        return handles[:n]
+
+    def erase(self, handles):
+        handles = np.ascontiguousarray(handles, np.int32).reshape(-1)
+        check(lib().ft_kfdb_erase(self._h, len(handles), ptr(handles) if len(handles) else None))
+
+    def clear(self):
+        check(lib().ft_kfdb_clear(self._h))
+
+    def size(self):
+        """-> (live keyframes, the words they hold)"""
+        n, w = C.c_int(), C.c_longlong()
+        check(lib().ft_kfdb_size(self._h, C.byref(n), C.byref(w)))
+        return n.value, w.value
+
+    def state(self, kind, handles):
+        """the stamp, word count and score the queries of `kind` left in the keyframes `handles` -> (int64, int32, float32)"""
+        handles = np.ascontiguousarray(handles, np.int32).reshape(-1)
+        n = len(handles)
+        stamps, words, scores = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
+        check(lib().ft_kfdb_state(self._h, kind, n, ptr(handles) if n else None, ptr(stamps), ptr(words), ptr(scores)))
+        return stamps[:n], words[:n], scores[:n]
+
+    def score(self, kind, query_id, ids, values, connected=()):
+        """The device part of a query (ft_kfdb_score).  -> dict(n_sharing, max_common_words, min_common_words, handles, words,
+        scores, raw_scores), the arrays for the scored keyframes in the order of lKFsSharingWords."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        values = np.ascontiguousarray(values, np.float64).reshape(-1)
+        assert len(ids) == len(values)
+        connected = np.ascontiguousarray(connected, np.int32).reshape(-1)
+        m = max(self.size()[0], 1)
+        ns, mx, mn, nsc = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        h, w, s, raw = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float32), np.zeros(m, np.float64)
+        check(lib().ft_kfdb_score(self._h, kind, int(query_id), len(ids), ptr(ids) if len(ids) else None,
+                                  ptr(values) if len(ids) else None, len(connected), ptr(connected) if len(connected) else None,
+                                  C.byref(ns), C.byref(mx), C.byref(mn), C.byref(nsc), ptr(h), ptr(w), ptr(s), ptr(raw)))
+        k = nsc.value
+        return dict(n_sharing=ns.value, max_common_words=mx.value, min_common_words=mn.value, handles=h[:k], words=w[:k],
+                    scores=s[:k], raw_scores=raw[:k])
+
+    @staticmethod
+    def _neighbours(scored, neighbours, maps):
+        """scored handles, neighbours(handle) -> handles in GetBestCovisibilityKeyFrames order, maps(handle) -> label"""
+        lists = [np.asarray(neighbours(int(h)), np.int32).reshape(-1) for h in scored]
+        offsets = np.zeros(len(lists) + 1, np.int32)
+        offsets[1:] = np.cumsum([len(v) for v in lists])
+        flat = np.ascontiguousarray(np.concatenate(lists + [np.zeros(0, np.int32)]), np.int32)
+        smap = np.array([maps(int(h)) for h in scored], np.int32)
+        nmap = np.array([maps(int(h)) for h in flat], np.int32)
+        return offsets, flat, smap, nmap
+
+    def select_n_best(self, query_id, scored, neighbours, maps, query_map, n_candidates, bad_maps=()):
+        """:671-729 on the result `scored` of score(PLACE, ...) -> (vpLoopCand, vpMergeCand) as handles"""
+        hs = np.ascontiguousarray(scored["handles"], np.int32)
+        sc = np.ascontiguousarray(scored["scores"], np.float32)
+        offsets, flat, smap, nmap = self._neighbours(hs, neighbours, maps)
+        bad = np.ascontiguousarray(bad_maps, np.int32).reshape(-1)
+        loop, merge = np.zeros(max(n_candidates, 1), np.int32), np.zeros(max(n_candidates, 1), np.int32)
+        nl, nm = C.c_int(), C.c_int()
+        check(lib().ft_kfdb_select_n_best(self._h, int(query_id), len(hs), ptr(hs), ptr(sc), ptr(offsets), ptr(flat), ptr(smap),
+                                          ptr(nmap), query_map, len(bad), ptr(bad) if len(bad) else None, n_candidates, ptr(loop),
+                                          C.byref(nl), ptr(merge), C.byref(nm)))
+        return loop[:nl.value], merge[:nm.value]
+
+    def select_reloc(self, query_id, scored, neighbours, maps, target_map):
+        """:792-844 on the result `scored` of score(RELOC, ...) -> vpRelocCandidates as handles"""
+        hs = np.ascontiguousarray(scored["handles"], np.int32)
+        sc = np.ascontiguousarray(scored["scores"], np.float32)
+        offsets, flat, smap, nmap = self._neighbours(hs, neighbours, maps)
+        out = np.zeros(max(len(hs), 1), np.int32)
+        n = C.c_int()
+        check(lib().ft_kfdb_select_reloc(self._h, int(query_id), len(hs), ptr(hs), ptr(sc), ptr(offsets), ptr(flat), ptr(smap),
+                                         ptr(nmap), target_map, ptr(out), C.byref(n)))
+        return out[:n.value]
+
+    def DetectNBestCandidates(self, query_id, ids, values, connected, neighbours, maps, query_map, n_candidates, bad_maps=()):
+        """KeyFrameDatabase::DetectNBestCandidates (:604-730): pKF as (mnId, mBowVec, GetConnectedKeyFrames, GetMap)"""
+        return self.select_n_best(query_id, self.score(self.PLACE, query_id, ids, values, connected), neighbours, maps, query_map,
+                                  n_candidates, bad_maps)
+
+    def DetectRelocalizationCandidates(self, query_id, ids, values, neighbours, maps, target_map):
+        """KeyFrameDatabase::DetectRelocalizationCandidates (:733-845): F as (mnId, mBowVec)"""
+        return self.select_reloc(query_id, self.score(self.RELOC, query_id, ids, values), neighbours, maps, target_map)
+
+
 class StereoFrontend:
     """Fused extract(left) + extract(right) + ComputeStereoMatches for batches of rectified pairs."""
 

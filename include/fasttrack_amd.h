@@ -960,6 +960,89 @@ FT_API int ft_distinctive_descriptors(ft_context *ctx, int n_points,
                                       int *best_index /* [n_points] */, int *best_median /* [n_points] or NULL */,
                                       uint8_t *out_descriptors /* n_points x 32 bytes or NULL */);
 
+/* ----------------------------------------------------------------------------------------------
+ * KeyFrameDatabase (src/KeyFrameDatabase.cc), device-resident: the step of the BoW chain between ft_bow_transform (a keyframe's
+ * BowVector) and ft_search_by_bow_keyframes / ft_search_by_bow (which consume the candidates of a place-recognition query).
+ * Ported are the two queries with a caller: DetectNBestCandidates (:604-730; LoopClosing.cc:491) and
+ * DetectRelocalizationCandidates (:733-845; Tracking.cc:3810), with L1Scoring::score
+ * (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68).  DetectCandidates, DetectBestCandidates and DetectLoopCandidates have no
+ * caller and stay out.
+ *
+ * There is no inverted file: a wave per stored keyframe intersects two sorted word lists, so add is an append and erase a
+ * tombstone.  A HANDLE is the add sequence number of a keyframe (0, 1, 2, ... over the database's lifetime; never reused).
+ * ft_kfdb_create: scoring uses the reference's enum (BowVector.h); 0 (L1_NORM, what ORBvoc uses) is implemented, anything else
+ *   is FT_ERR_INVALID.  The database counts as an object of its context: ft_context_destroy refuses while it is alive.
+ * ft_kfdb_add (:39-45): n BowVectors in CSR form - keyframe k owns bow_ids / bow_values [bow_offsets[k], bow_offsets[k + 1]),
+ *   ids strictly ascending, exactly what ft_bow_transform returns; a vector may be empty.  handles_out[k] = its handle.  Ids and
+ *   values are stored in two device arrays; storage grows by doubling and keeps its contents.
+ * ft_kfdb_erase (:47-66): a tombstone.  An unknown or already erased handle (also: twice in one call) is FT_ERR_INVALID and
+ *   nothing is erased.  clearMap (:74-98) is an erase of that map's handles.  KeyFrame::SetBadFlag erases (KeyFrame.cc:678), so
+ *   the database never holds a bad keyframe: the isBad() test at :712 is the caller's.  When the words of erased keyframes
+ *   exceed half of the stored words, the rows are compacted in handle order (statistic kfdb.compactions).
+ * ft_kfdb_clear (:68-72): every keyframe goes; handles keep counting.
+ * ft_kfdb_size: live keyframes and the words they hold.
+ *
+ * Per keyframe and per query KIND (0 place recognition: mnPlaceRecognitionQuery / mnPlaceRecognitionWords /
+ * mPlaceRecognitionScore; 1 relocalisation: mnRelocQuery / mnRelocWords / mRelocScore) the database keeps the reference's three
+ * members, 0 when a keyframe is added (KeyFrame.cc:33-34).  THEY PERSIST BETWEEN QUERIES, as in the reference: :689 adds the
+ * stored score of a neighbour that was stamped by this query but not scored in it - whatever an earlier query left.
+ * ft_kfdb_state reads them (from the host mirror the last query of that kind left; no device access).
+ *
+ * ft_kfdb_score: the device part of a query, :615-666 (kind 0, with the connected set spConnectedKF as handles) or :741-787
+ *   (kind 1, n_connected must be 0).  For every live keyframe that shares at least one word with the query: a stamp that differs
+ *   from query_id resets the count, and the keyframe - unless connected - is stamped and LISTED; the count then grows by the
+ *   shared words.  A connected keyframe ends with count 1 and its stamp unchanged; a keyframe already stamped with query_id is
+ *   not listed again and its count accumulates.  maxCommonWords is taken over the listed keyframes,
+ *   minCommonWords = (int)(maxCommonWords * 0.8f) (one fp32 product, truncated), and a listed keyframe is scored when its
+ *   count is strictly greater.  The score: the terms (|vi - wi| - |vi|) - |wi| of the common words, vi the query's value, added
+ *   in ascending word order into one double; -sum / 2.0; rounded to float; written to the keyframe's state.
+ *   Outputs: n_sharing (listed keyframes), max_common_words, min_common_words, n_scored, and for the scored keyframes, in the
+ *   order of lKFsSharingWords (first encounter walking the query's words ascending and each word's list in insertion order =
+ *   ascending (first shared word, handle)): scored_handles, scored_words, scored_scores and - may be NULL - raw_scores, the
+ *   double before the rounding to float.  Each array holds up to n_live entries.
+ *   One block up, TWO launches whatever the number of keyframes or words (kernel.kfdb_count, kernel.kfdb_score), the records and
+ *   the state of the kind down, one wait; statistics kfdb_score.total, kfdb_score.launches.  n_words == 0, an empty database or
+ *   one whose keyframes hold no word: zeros without a launch.
+ *   FT_ERR_INVALID: query ids not strictly ascending, a connected handle that is not live, null arrays with non-zero counts,
+ *   kind outside {0, 1}.  FT_ERR_CAPACITY: a query of more than FT_KFDB_MAX_QUERY_WORDS words (2 x nFeatures = 4 000 fits).
+ *
+ * The selection calls are host code (no launch, no device access); they read the state the scoring call left.  They need
+ * GetBestCovisibilityKeyFrames(10) and GetMap() of the SCORED keyframes only, which the caller gathers: neighbours of scored
+ * keyframe i are neigh_handles[neigh_offsets[i] .. neigh_offsets[i + 1]) in the reference's order, maps are any integer labels.
+ * ft_kfdb_select_n_best (:671-729): float accumulation over the neighbours in the given order; a neighbour counts only when its
+ *   stamp equals query_id and then adds its STORED score; pBestKF moves on a strict >; a STABLE descending sort on the
+ *   accumulated score; the walk deduplicates by keyframe, splits loop (same map as query_map) from merge candidates, skips
+ *   merge candidates of a map in bad_maps and stops when both lists hold n_candidates.  loop_out / merge_out hold n_candidates.
+ * ft_kfdb_select_reloc (:792-844): the same accumulation on the relocalisation state; minScoreToRetain = 0.75f * bestAccScore;
+ *   entries strictly greater, in list order (no sort), of the given map, deduplicated.  out holds n_scored.
+ * A scored or neighbour handle that is erased or unknown is FT_ERR_INVALID.
+ * ---------------------------------------------------------------------------------------------- */
+#define FT_KFDB_MAX_QUERY_WORDS 4096
+#define FT_KFDB_PLACE_RECOGNITION 0
+#define FT_KFDB_RELOCALIZATION 1
+typedef struct ft_kfdb ft_kfdb;
+FT_API int ft_kfdb_create(ft_context *ctx, int scoring, ft_kfdb **out);
+FT_API int ft_kfdb_destroy(ft_kfdb *db);
+FT_API int ft_kfdb_add(ft_kfdb *db, int n, const int *bow_offsets /* [n + 1], bow_offsets[0] == 0 */, const unsigned *bow_ids,
+                       const double *bow_values, int *handles_out /* [n] */);
+FT_API int ft_kfdb_erase(ft_kfdb *db, int n, const int *handles);
+FT_API int ft_kfdb_clear(ft_kfdb *db);
+FT_API int ft_kfdb_size(const ft_kfdb *db, int *n_live, long long *n_words);
+FT_API int ft_kfdb_state(const ft_kfdb *db, int kind, int n, const int *handles, long long *stamps /* [n] or NULL */,
+                         int *words /* [n] or NULL */, float *scores /* [n] or NULL */);
+FT_API int ft_kfdb_score(ft_kfdb *db, int kind, long long query_id, int n_words, const unsigned *ids, const double *values,
+                         int n_connected, const int *connected_handles, int *n_sharing, int *max_common_words,
+                         int *min_common_words, int *n_scored, int *scored_handles /* [n_live] */, int *scored_words /* [n_live] */,
+                         float *scored_scores /* [n_live] */, double *raw_scores /* [n_live] or NULL */);
+FT_API int ft_kfdb_select_n_best(const ft_kfdb *db, long long query_id, int n_scored, const int *scored_handles,
+                                 const float *scored_scores, const int *neigh_offsets /* [n_scored + 1] */, const int *neigh_handles,
+                                 const int *scored_map /* [n_scored] */, const int *neigh_map, int query_map, int n_bad_maps,
+                                 const int *bad_maps, int n_candidates, int *loop_out, int *n_loop, int *merge_out, int *n_merge);
+FT_API int ft_kfdb_select_reloc(const ft_kfdb *db, long long query_id, int n_scored, const int *scored_handles,
+                                const float *scored_scores, const int *neigh_offsets /* [n_scored + 1] */, const int *neigh_handles,
+                                const int *scored_map /* [n_scored] */, const int *neigh_map, int map, int *out /* [n_scored] */,
+                                int *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,8 +12,10 @@
 // setGPURunMode flags of the reference have no equivalent.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <cstdio>
@@ -745,5 +747,114 @@ inline std::vector<int> ComputeDistinctiveDescriptors(Context &ctx, const std::v
     if (bestMedian) bestMedian->resize(np);
     return bestIdx;
 }
+
+// KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc) resident on the device (ft_kfdb_*): add, erase, clear,
+// DetectNBestCandidates (:604-730) and DetectRelocalizationCandidates (:733-845), the two queries with a caller.  A keyframe is
+// known by the handle add returns (keep it beside the KeyFrame*: `int mnDatabaseHandle`).  mnPlaceRecognitionQuery / Words /
+// Score and the mnReloc* set live in the database and persist between queries, as they do in the KeyFrame.  What the queries
+// read from host state that changes between them comes in through two callbacks, asked for the SCORED keyframes only:
+//   neighbours(handle) = the handles of pKFi->GetBestCovisibilityKeyFrames(10), in that order;
+//   mapOf(handle)      = an integer label of pKFi->GetMap() (the map's mnId).
+// KeyFrame::SetBadFlag erases (KeyFrame.cc:678), so the database holds no bad keyframe and the isBad() test of :712 has no
+// counterpart; clearMap(pMap) (:74-98) is erase() of that map's handles.
+class KeyFrameDatabase {
+public:
+    typedef std::function<std::vector<int>(int)> NeighboursFn;
+    typedef std::function<int(int)> MapFn;
+    explicit KeyFrameDatabase(Context &ctx, int scoring = 0) { check(ft_kfdb_create(ctx.handle(), scoring, &h_)); }
+    ~KeyFrameDatabase() { ft_kfdb_destroy(h_); }
+    KeyFrameDatabase(const KeyFrameDatabase &) = delete;
+    KeyFrameDatabase &operator=(const KeyFrameDatabase &) = delete;
+    ft_kfdb *handle() const { return h_; }
+
+    // void add(KeyFrame *pKF): pKF->mBowVec -> the keyframe's handle
+    int add(const ORBVocabulary::BowVector &mBowVec) {
+        std::vector<unsigned> ids;
+        std::vector<double> values;
+        flatten(mBowVec, ids, values);
+        const int offsets[2] = {0, (int)ids.size()};
+        int handle = -1;
+        check(ft_kfdb_add(h_, 1, offsets, ids.data(), values.data(), &handle));
+        return handle;
+    }
+    void erase(int handle) { check(ft_kfdb_erase(h_, 1, &handle)); }
+    void erase(const std::vector<int> &handles) { check(ft_kfdb_erase(h_, (int)handles.size(), handles.data())); }  // clearMap
+    void clear() { check(ft_kfdb_clear(h_)); }
+    int size() const {
+        int n = 0;
+        check(ft_kfdb_size(h_, &n, nullptr));
+        return n;
+    }
+
+    // void DetectNBestCandidates(KeyFrame *pKF, vector<KeyFrame*> &vpLoopCand, vector<KeyFrame*> &vpMergeCand, int nNumCandidates):
+    // pKF as mnId, mBowVec, the handles of GetConnectedKeyFrames() and the label of GetMap(); badMaps: labels of maps with IsBad()
+    void DetectNBestCandidates(long long mnId, const ORBVocabulary::BowVector &mBowVec, const std::vector<int> &vConnected, int map,
+                               const NeighboursFn &neighbours, const MapFn &mapOf, std::vector<int> &vpLoopCand,
+                               std::vector<int> &vpMergeCand, int nNumCandidates, const std::vector<int> &badMaps = {}) {
+        Scored s = score(FT_KFDB_PLACE_RECOGNITION, mnId, mBowVec, vConnected);
+        gather(s, neighbours, mapOf);
+        vpLoopCand.assign((size_t)std::max(nNumCandidates, 1), -1);
+        vpMergeCand.assign((size_t)std::max(nNumCandidates, 1), -1);
+        int nLoop = 0, nMerge = 0;
+        check(ft_kfdb_select_n_best(h_, mnId, (int)s.handles.size(), s.handles.data(), s.scores.data(), s.offsets.data(), s.neigh.data(),
+                                    s.maps.data(), s.neighMaps.data(), map, (int)badMaps.size(), badMaps.data(), nNumCandidates,
+                                    vpLoopCand.data(), &nLoop, vpMergeCand.data(), &nMerge));
+        vpLoopCand.resize(nLoop);
+        vpMergeCand.resize(nMerge);
+    }
+
+    // vector<KeyFrame*> DetectRelocalizationCandidates(Frame *F, Map *pMap): F as mnId and mBowVec
+    std::vector<int> DetectRelocalizationCandidates(long long mnId, const ORBVocabulary::BowVector &mBowVec, int map,
+                                                    const NeighboursFn &neighbours, const MapFn &mapOf) {
+        Scored s = score(FT_KFDB_RELOCALIZATION, mnId, mBowVec, {});
+        gather(s, neighbours, mapOf);
+        std::vector<int> out(s.handles.size() + 1, -1);
+        int n = 0;
+        check(ft_kfdb_select_reloc(h_, mnId, (int)s.handles.size(), s.handles.data(), s.scores.data(), s.offsets.data(), s.neigh.data(),
+                                   s.maps.data(), s.neighMaps.data(), map, out.data(), &n));
+        out.resize(n);
+        return out;
+    }
+
+private:
+    struct Scored {
+        std::vector<int> handles, words, offsets, neigh, maps, neighMaps;
+        std::vector<float> scores;
+    };
+    static void flatten(const ORBVocabulary::BowVector &v, std::vector<unsigned> &ids, std::vector<double> &values) {
+        ids.reserve(v.size() + 1);
+        values.reserve(v.size() + 1);
+        for (const auto &e : v) ids.push_back(e.first), values.push_back(e.second);
+    }
+    Scored score(int kind, long long mnId, const ORBVocabulary::BowVector &mBowVec, const std::vector<int> &vConnected) {
+        std::vector<unsigned> ids;
+        std::vector<double> values;
+        flatten(mBowVec, ids, values);
+        Scored s;
+        const size_t room = (size_t)size() + 1;
+        s.handles.resize(room);
+        s.words.resize(room);
+        s.scores.resize(room);
+        int nSharing = 0, maxWords = 0, minWords = 0, nScored = 0;
+        check(ft_kfdb_score(h_, kind, mnId, (int)ids.size(), ids.data(), values.data(), (int)vConnected.size(), vConnected.data(),
+                            &nSharing, &maxWords, &minWords, &nScored, s.handles.data(), s.words.data(), s.scores.data(), nullptr));
+        s.handles.resize(nScored);
+        s.words.resize(nScored);
+        s.scores.resize(nScored);
+        return s;
+    }
+    static void gather(Scored &s, const NeighboursFn &neighbours, const MapFn &mapOf) {
+        s.offsets.assign(1, 0);
+        for (int h : s.handles) {
+            for (int h2 : neighbours(h)) s.neigh.push_back(h2), s.neighMaps.push_back(mapOf(h2));
+            s.offsets.push_back((int)s.neigh.size());
+            s.maps.push_back(mapOf(h));
+        }
+        s.neigh.push_back(-1);  // (never read: data() of an empty vector may be null)
+        s.neighMaps.push_back(-1);
+        s.maps.push_back(-1);
+    }
+    ft_kfdb *h_ = nullptr;
+};
 
 }  // namespace fasttrack
