@@ -591,6 +591,9 @@ __device__ __forceinline__ unsigned fast_score2(unsigned v, const unsigned p[16]
 #ifndef FC_WAVES_PER_EU
 #define FC_WAVES_PER_EU 1
 #endif
+#ifndef FC_LEAN_APPEND
+#define FC_LEAN_APPEND 1  // ring append of the unordered pass: 1 = lanes leave the loop with their last candidate, 0 = all lanes stay and the idle ones write the spare entry
+#endif
 __host__ __device__ __forceinline__ int fc_pitch(int wCell, int TP) { return TP ? TP : ((wCell + 12) & ~3); }
 __host__ __device__ __forceinline__ int fc_tile_bytes(int wCell, int hCell, int TP) {
     // the flags of the slow path need one byte per tested pixel
@@ -821,8 +824,8 @@ __global__ __launch_bounds__(64, FC_WAVES_PER_EU) void k_fast_cells(FtGeom g, co
     if constexpr (TP > 0 && !ORDERED) {
         // Two half-cells side by side: lanes 0-31 walk the rows of the upper half, lanes 32-63 the rows of the lower
         // half, 32 columns each (a 36-pixel-wide cell fills 56 % of a 64-lane row, two 32-wide halves fill it); the
-        // columns beyond 32 are tested afterwards in linear order.  Inside a half the rows slide as in the ordered
-        // pass (shared vertical differences, immediates only).
+        // columns beyond 32 go through the same form in bands of their own (below).  Inside a half the rows slide as in the
+        // ordered pass (shared vertical differences, immediates only).
         const int half = lane >> 5, cx = lane & 31;
         const int hRows = (ph + 1) >> 1;          // rows of the upper half; the lower half has ph - hRows
         const int y0h = half * hRows;              // first row of this lane's half
@@ -838,13 +841,31 @@ __global__ __launch_bounds__(64, FC_WAVES_PER_EU) void k_fast_cells(FtGeom g, co
         unsigned hist0 = __builtin_amdgcn_sad_hi_u8(pA, (unsigned)col[0], 0u);
         unsigned hist1 = __builtin_amdgcn_sad_hi_u8(pC, (unsigned)col[2 * TP], __builtin_amdgcn_sad_u8(pB, (unsigned)col[TP], 0u));
         const unsigned th = (unsigned)minTh;
-        const int rowsHalf = half ? ph - hRows : hRows;
-        // blocks of at most 28 rows (seven trips): a lane's verdicts of a block fit one 32-bit mask
-        for (int yb = 0; yb < hRows; yb += 28) {
-        const int yEnd = min(yb + 28, hRows);
-        unsigned cmask = 0;
-        auto trip = [&](int y) {
-            const uint8_t *r = col + y * TP;
+        const int rowsHalf = actC ? (half ? ph - hRows : hRows) : 0;  // rows of this lane's column (none beyond the cell)
+        // a lane's valid verdicts: cnt rows (clamped to 0 .. n; n <= T, both wave-uniform) at the top of a T-bit mask - three instructions
+        auto validMask = [](int cnt, int n, int T) -> unsigned {
+            int c;
+            unsigned m;
+            asm("v_med3_i32 %0, %1, 0, %2" : "=v"(c) : "v"(cnt), "s"(n));
+            asm("v_bfm_b32 %0, %1, %2" : "=v"(m) : "v"(c), "v"(T - c));
+            return m;
+        };
+        // The columns beyond 32 (wRem of them: 4 to 6 of a 36 to 38 pixel cell) go through the same packed sliding form in
+        // a pass of their own: a lane takes (remainder column, band of rows), nbR = 64 / wRem bands of bR = ceil(ph / nbR)
+        // rows - one trip of four rows on the usual cells (16 x 3, 12 x 4, 10 x 4), two or more on tall bands.  Every
+        // width up to the 23 columns of a 64-byte pitch takes this form, there is no linear pass any more: by instruction
+        // count (a trip costs about as much as one and a half 64-pixel rounds of the linear pass did and covers four rows
+        // of up to 64 lanes) it is ahead at every wRem.  A band is never taller than a half (nbR >= 2), so the bands walk
+        // their rows block by block beside the halves and share every block's scan.
+        const int wRem = pw - wMain;
+        const unsigned remMagic = div_magic_small((unsigned)wRem);
+        int nbR = 0, bR = 0;
+        if (wRem > 0) {  // wave-uniform scalar arithmetic, two table loads
+            nbR = div_by(64, remMagic);
+            bR = div_by(ph + nbR - 1, div_magic_small((unsigned)nbR));
+        }
+        // four rows of a lane's column: r = the column at the trip's first row, the rest is the lane's sliding state
+        auto trip4 = [&](const uint8_t *r, unsigned &pA, unsigned &pB, unsigned &pC, unsigned &hist0, unsigned &hist1, unsigned &cmask) {
             unsigned pv[7];
             pv[0] = pA; pv[1] = pB; pv[2] = pC;
 #pragma unroll
@@ -873,6 +894,11 @@ __global__ __launch_bounds__(64, FC_WAVES_PER_EU) void k_fast_cells(FtGeom g, co
                 : "v"(M0), "v"(th), "v"(M1)
                 : "vcc");
         };
+        // blocks of at most 28 rows (seven trips): a lane's verdicts of a block fit one 32-bit mask
+        for (int yb = 0; yb < hRows; yb += 28) {
+        const int yEnd = min(yb + 28, hRows);
+        unsigned cmask = 0;
+        auto trip = [&](int y) { trip4(col + y * TP, pA, pB, pC, hist0, hist1, cmask); };
         // two trips per iteration: the register rotation (pA / pB / pC, the two history pairs) between them is renaming
         // instead of four moves per trip
         int y = yb;
@@ -881,19 +907,41 @@ __global__ __launch_bounds__(64, FC_WAVES_PER_EU) void k_fast_cells(FtGeom g, co
             trip(y + 4);
         }
         if (y < yEnd) trip(y);
-        {
-            // row yb + r of a half sits at bit T - 1 - r (T = rows walked in the block, a multiple of four); rows the half does
-            // not have and columns beyond the cell are masked out here, once
-            const int T = (yEnd - yb + 3) & ~3;
-            const int cnt = min(max(rowsHalf - yb, 0), T);
-            const unsigned valid = actC ? (((1u << cnt) - 1u) << (T - cnt)) : 0u;
-            cmask &= valid;
-            const int codeTop = codeBase + ((yb + T - 1) << 6);
-            // Emission.  The lanes' candidate counts are scanned once (six DPP adds), which gives every lane the ring slot of
-            // its first candidate; then every lane writes its own candidates one after the other, lowest bit first - as many
-            // rounds as the fullest column holds candidates, each round five vector instructions, a write and the loop test
-            // (a ballot + popcount + position per round, as the rows used to cost, is what this avoids).
-            int incl = __popc(cmask);
+        // The remainder bands walk rows yb .. yb + 27 of their own beside the block (a band has no more rows than a half, and
+        // on every workload's cells one block holds them all): their verdicts go into a second mask and share the block's
+        // scan.  Row yb + r of a band sits at bit TR - 1 - r, as in the halves.
+        unsigned rmask = 0;
+        int codeTopR = 0;
+        if (yb < bR) {  // wave-uniform (bR = 0 without remainder columns)
+            // (the lane number is made opaque so that the band arithmetic is not hoisted out of the block loop: it would sit
+            // in registers across phase B, where the kernel's register peak is, for a second block that hardly any cell has)
+            int laneR = lane;
+            asm volatile("" : "+v"(laneR));
+            const int band = div_by(laneR, remMagic), rc = vmad24(band, -wRem, laneR);
+            const int yy = vmad24(band, bR, yb);  // first row of the band in this block; bands beyond the cell (and the lanes
+                                                  // behind the last band: nbR * bR >= ph) walk rows at its end, all masked out
+            const uint8_t *rcol = (t0 + 35) + vmad24(min(yy, ph), TP, rc);  // (x + 3, tile row yy), x = 32 + rc
+            unsigned qA = rcol[3 * TP], qB = rcol[4 * TP], qC = rcol[5 * TP];
+            unsigned h0 = __builtin_amdgcn_sad_hi_u8(qA, (unsigned)rcol[0], 0u);
+            unsigned h1 = __builtin_amdgcn_sad_hi_u8(qC, (unsigned)rcol[2 * TP], __builtin_amdgcn_sad_u8(qB, (unsigned)rcol[TP], 0u));
+            const int nR = min(bR - yb, 28);
+            trip4(rcol, qA, qB, qC, h0, h1, rmask);  // (the usual band is done with it)
+            for (int yr = 4; yr < nR; yr += 4) trip4(rcol + (unsigned)(yr * TP), qA, qB, qC, h0, h1, rmask);
+            const int TR = (nR + 3) & ~3;
+            rmask &= validMask(ph - yy, nR, TR);
+            codeTopR = ((yy << 6) + rc) + (((TR - 1) << 6) + 32);
+        }
+        // row yb + r of a half sits at bit T - 1 - r (T = rows walked in the block, a multiple of four); rows the half does
+        // not have and columns beyond the cell are masked out here, once
+        const int T = (yEnd - yb + 3) & ~3;
+        cmask &= validMask(rowsHalf - yb, T, T);
+        const int codeTop = codeBase + ((yb + T - 1) << 6);
+        if (!FC_LEAN_APPEND || __builtin_amdgcn_ballot_w64((cmask | rmask) != 0u)) {  // wave-uniform: a flat block has nothing to scan or append
+            // Emission.  The lanes' candidate counts (both masks) are scanned once (six DPP adds), which gives every lane the
+            // ring slot of its first candidate; then every lane writes its own candidates one after the other, lowest bit
+            // first, those of its half before those of its remainder band - as many rounds as the fullest lane holds
+            // candidates (a ballot + popcount + position per round, as the rows used to cost, is what this avoids).
+            int incl = __popc(cmask) + __popc(rmask);
             const int own = incl;
             incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, true);  // row_shr:1
             incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, true);  // row_shr:2
@@ -902,49 +950,56 @@ __global__ __launch_bounds__(64, FC_WAVES_PER_EU) void k_fast_cells(FtGeom g, co
             incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, true);  // row_bcast:15 into rows 1 and 3
             incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, true);  // row_bcast:31 into rows 2 and 3
             const int total = __builtin_amdgcn_readlane(incl, 63);
-            // (every step leaves room for one more round of 64 in the ring: the appends of the remaining columns rely on it)
             if (nc + total > FC_CAND - 64) flushB();  // wave-uniform; leaves nc = 0
             if (total <= FC_CAND - 64) {
                 unsigned short *slot = cand + (nc + incl - own);
-                while (__builtin_amdgcn_ballot_w64(cmask != 0u)) {  // wave-uniform
-                    // a lane whose mask is empty writes the spare entry behind the lists: no exec juggling in the loop
-                    *(cmask ? slot : cand + (FC_CAND + FC_CORN)) = (unsigned short)(codeTop - (__builtin_ctz(cmask | 0x80000000u) << 6));
-                    cmask &= cmask - 1u;
-                    slot++;
-                }
+#if FC_LEAN_APPEND
+                // A lane leaves the loop (its exec bit) with its last candidate: six vector instructions and a write per round,
+                // the exec bookkeeping is scalar.  The slot pointer of a lane ends behind its last main candidate, where its
+                // remainder candidates go.
+                auto append = [&](unsigned m, int top) {
+                    if (m) {
+                        do {
+                            *slot = (unsigned short)vmad24(__builtin_ctz(m), -64, top);
+                            slot++;
+                            m &= m - 1u;
+                        } while (m);
+                    }
+                };
+#else
+                auto append = [&](unsigned m, int top) {
+                    unsigned short *s = slot;
+                    slot += __popc(m);
+                    while (__builtin_amdgcn_ballot_w64(m != 0u)) {  // wave-uniform
+                        // a lane whose mask is empty writes the spare entry behind the lists: no exec juggling in the loop
+                        *(m ? s : cand + (FC_CAND + FC_CORN)) = (unsigned short)(top - (__builtin_ctz(m | 0x80000000u) << 6));
+                        m &= m - 1u;
+                        s++;
+                    }
+                };
+#endif
+                append(cmask, codeTop);
+                append(rmask, codeTopR);
                 nc += total;
             } else {
                 // more candidates in one block than the ring holds (dense texture): a round per candidate rank with a flush
                 // whenever the ring fills
-                for (;;) {
-                    const unsigned long long b = __builtin_amdgcn_ballot_w64(cmask != 0u);
-                    if (!b) break;  // wave-uniform
-                    const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, (unsigned)nc));
-                    const int bit = __builtin_ctz(cmask | 0x80000000u);
-                    if (__builtin_amdgcn_inverse_ballot_w64(b)) cand[pos] = (unsigned short)(codeTop - (bit << 6));
-                    cmask &= cmask - 1u;
-                    nc += __popcll(b);
-                    if (nc > FC_CAND - 64) flushB();  // wave-uniform
+                for (int part = 0; part < 2; part++) {
+                    unsigned m = part ? rmask : cmask;
+                    const int top = part ? codeTopR : codeTop;
+                    for (;;) {
+                        const unsigned long long b = __builtin_amdgcn_ballot_w64(m != 0u);
+                        if (!b) break;  // wave-uniform
+                        const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, (unsigned)nc));
+                        const int bit = __builtin_ctz(m | 0x80000000u);
+                        if (__builtin_amdgcn_inverse_ballot_w64(b)) cand[pos] = (unsigned short)(top - (bit << 6));
+                        m &= m - 1u;
+                        nc += __popcll(b);
+                        if (nc > FC_CAND - 64) flushB();  // wave-uniform
+                    }
                 }
             }
         }
-        }
-        // columns 32 .. pw-1 (four of them for a 36-pixel cell), every row, in linear order
-        const int wRem = pw - wMain, nRem = wRem * ph;
-        if (wRem > 0) {
-            const unsigned remMagic = div_magic_small((unsigned)wRem);
-            for (int base = 0; base < nRem; base += 64) {
-                const int i = base + lane;
-                const int ii = min(i, nRem - 1);
-                const int yy = div_by(ii, remMagic), xx = wMain + ii - yy * wRem;
-                const uint8_t *cpx = t0 + (yy + 3) * TP + (xx + 3);
-                const unsigned v = cpx[0];
-                const unsigned m0 = max(FT_AD(0, 3), FT_AD(0, -3));
-                const unsigned m1 = max(FT_AD(3, 0), FT_AD(-3, 0));
-                const unsigned m01r = i < nRem ? min(m0, m1) : 0u;
-                if (__any(m01r > (unsigned)minTh)) nc = pushRow(m01r > (unsigned)minTh, pixCode(yy, xx), nc);
-                if (nc > FC_CAND - 64) flushB();  // wave-uniform
-            }
         }
         flushB();
     } else if constexpr (TP > 0) {
