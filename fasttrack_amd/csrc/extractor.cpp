@@ -1,7 +1,7 @@
 // Host orchestration of the ORB extractor: replaces ORB_SLAM3::ORBextractor (reference
 // include/ORBextractor.h:100-197, src/ORBextractor.cc).  Geometry/tables are computed here exactly as
 // the reference's CPU branch does (float arithmetic, cvRound = half-to-even); pixels are only ever
-// touched by the HIP kernels in kernels_extract.hip.  Compiled with -ffp-contract=off.
+// touched by the HIP kernels in kernels_pyramid.hip, kernels_fast.hip and kernels_orient_desc.hip.  Compiled with -ffp-contract=off.
 #include <algorithm>
 #include <map>
 #include <memory>

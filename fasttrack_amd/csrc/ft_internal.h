@@ -183,7 +183,7 @@ const char *ft_debug_env(const char *name);  // FT_DEBUG_* aids only (context.cp
         if (_e != hipSuccess) return ft_hip_fail(_e, #call, __FILE__, __LINE__);  \
     } while (0)
 
-// ---- kernel launchers (kernels_extract.hip) -------------------------------------------------
+// ---- kernel launchers (kernels_pyramid.hip, kernels_fast.hip, kernels_orient_desc.hip, kernels_octree.hip) ----
 // The one-launch pyramid (k_pyr_cascade): an image is cut into K horizontal bands, a workgroup of PC_WAVES waves owns one band
 // through all levels.  rows[level][band] = first | end << 16 of the band's row range at that level (levels 1 .. n - 1).
 // Two bands of sixteen waves: measured on the default bench against 1 x 8 / 1 x 16 / 2 x 4 / 2 x 8 / 2 x 12 / 3 x 8 / 4 x 4 / 4 x 8 /
@@ -227,7 +227,6 @@ int ft_launch_blur_level(hipStream_t st, const uint8_t *img, int pitch, int w, i
 size_t ft_octree_smem_bytes(int poolCap, bool compact = false);
 size_t ft_octree_hist_smem_bytes(int poolCap);
 int ft_octree_big_keys(int poolCap);
-size_t ft_fast_smem_bytes(const FtGeom &g);
 
 // ---- kernel launchers (kernels_match.hip) ---------------------------------------------------
 // A right keypoint as k_stereo_rowsort lays it down in row-bucket order: everything the left keypoint's scan needs in

@@ -28,6 +28,7 @@
 // the host redoes that image with the host octree (extractor.cpp ft_extract_repair_*).
 #include "ft_internal.h"
 #include "octree_paths.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -35,11 +36,6 @@ using ft::op::kMaxDepth;
 using ft::op::Roots;
 using ft::op::SortElem;
 using ft::op::SortFrame;
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // exclusive prefix sum over the wave; total = sum of all lanes.  Six DPP adds (shifts inside the rows of 16 lanes, then the
 // row totals broadcast into the following rows) - as six __shfl_up it was six ds_bpermute round trips, and the rounds

@@ -96,11 +96,6 @@ __device__ __forceinline__ void wave_two_min(unsigned long long &k0, unsigned lo
     k1 = m1;
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // ---- candidate cache of the claim iteration (FtClaims::cache) ----
 // One LDS counter per wave hands out the positions while a window is scanned (the candidates turn up in divergent code).
 struct CacheBuild {

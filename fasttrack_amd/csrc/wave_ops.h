@@ -23,6 +23,13 @@ __device__ __forceinline__ void gstore(void *p, T v) {
 // loads instead of 64 identical VALU lanes.
 __device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
+// LDS hand-off between the lanes of ONE wave: the LDS queue of a wave is served in order, so only the
+// compiler has to be kept from moving accesses across this point.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 // Sum / minimum over the 64 lanes, returned wave-uniform: four DPP steps (lane pairs, quads, half rows, rows of 16;
 // all four are permutations inside a row, so no lane reads an invalid source) and one v_readlane per row - instead of
 // six shuffles through the LDS crossbar with their address arithmetic.

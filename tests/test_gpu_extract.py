@@ -343,6 +343,45 @@ def test_device_octree_equals_host_octree(ctx, monkeypatch):
             assert hm == om and dm == om
 
 
+def _fast_pitch_classes(ex, levels):
+    """LDS tile pitch of k_fast_cells per level that has cells (48, 64, 0 = the any-size variant), from the extractor's own
+    level sizes: borders of 16 px, cell columns of 35 px or more, wCell = ceil(width / nCols) (ORBextractor.cc:1128-1134),
+    and a tile row of wCell + 6 pixels + 3 of alignment"""
+    out = []
+    for level in range(levels):
+        lw, lh = ex.level_size(level)
+        ncols, nrows = (lw - 32) // 35, (lh - 32) // 35
+        if ncols > 0 and nrows > 0:
+            need = -(-(lw - 32) // ncols) + 9
+            out.append(48 if need <= 48 else 64 if need <= 64 else 0)
+    return out
+
+
+@pytest.mark.parametrize("w,h,sf,levels,classes", [
+    (112, 126, 1.05, 2, [64, 48]),   # two launches, one per pitch
+    (97, 83, 1.2, 3, [0, 64]),       # level 0 is a single cell column of 65 pixels: one launch of the any-size variant
+])
+@pytest.mark.parametrize("device_octree", [1, 0], ids=["unordered", "ordered"])
+def test_fast_launch_shapes_under_both_octrees(ctx, w, h, sf, levels, classes, device_octree):
+    """the split launch (48 + 64) and the any-size variant of k_fast_cells, each in front of the device octree (candidates in
+    any order) and of the host octree (row-major), as one image (cells dealt to the XCDs in runs, one keypoint per wave of
+    k_orient_desc) and as a launch of eight (image -> XCD, two keypoints per wave): keypoints, angles and descriptors equal the
+    oracle's bit for bit"""
+    nf = 300
+    with ctx.options(device_octree=device_octree):
+        ex = orb.ORBextractor(ctx, nf, sf, levels, 20, 7, w, h, max_batch=8)
+    assert _fast_pitch_classes(ex, levels) == classes
+    imgs = [synth.make_image(w, h, seed=700 + w + b, density=6.0) for b in range(5)] + [synth.make_noise(w, h, seed=705 + b) for b in range(3)]
+    oex = ob.Extractor(nf, sf, levels)
+    want = [oex.extract(img) for img in imgs]
+    assert all(len(ok) >= 10 for ok, _, _ in want) and sum(len(ok) for ok, _, _ in want) > 700
+    for batch in ([imgs[0]], imgs):
+        for (gk, gd, gm), (ok, od, om) in zip(ex.extract_batch(batch), want):
+            _check_same(gk, gd, ok, od)
+            assert gm == om
+    ex.close()
+
+
 def test_device_octree_overflow_falls_back_to_host(ctx):
     """more candidates in one level than k_octree sorts in LDS (FT_OCT_MAXN = 4096): the kernel raises its
     overflow flag and the batch is redone with the host octree - same result as the oracle, and the next

@@ -8,8 +8,8 @@ compares PER KERNEL, whatever file a kernel lives in: the instruction stream wit
 resource symbols, and the kernel's entry in the code-object metadata (registers, scratch, LDS, kernarg layout).  A kernel's
 ordinal in its file is normalised away (.LBB<n>_k -> .LBB_k, .Lfunc_end<n>, the loop comments); .file / .ident / __hip_cuid_* lines belong to no
 kernel.  The data objects the files define (constant tables) are compared by name: the order in which a file's
-anonymous-namespace globals are emitted varies from one run of the same compile to the next (kernels_extract.hip), so whole
-files are not compared.  Both trees are compiled at the same path by the same command line, one after the other.
+anonymous-namespace globals are emitted varies from one run of the same compile to the next (kernels_orient_desc.hip), so whole
+files are not compared; a table that a header hands to several files (c_divMagic of extract_dev.h) has to be the same in every one.  Both trees are compiled at the same path by the same command line, one after the other.
 Exit status 0: same kernels and objects, all identical.
 """
 import concurrent.futures

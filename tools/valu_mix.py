@@ -30,13 +30,13 @@ DEAR = 4.33
 
 # (file, symbol fragment, name in the profiles)
 KERNELS = [
-    ("kernels_extract.hip", "k_fast_cellsILi48ELb0EE", "k_fast_cells<48, false>"),
-    ("kernels_extract.hip", "k_fast_cellsILi64ELb0EE", "k_fast_cells<64, false>"),
-    ("kernels_extract.hip", "k_orient_descILi2EE", "k_orient_desc<2>"),
-    ("kernels_extract.hip", "k_pyr_rowsILb0EE", "k_pyr_rows<false>"),
-    ("kernels_extract.hip", "k_pyr_rowsILb1EE", "k_pyr_rows<true>"),
-    ("kernels_extract.hip", "13k_pyr_cascadeE", "k_pyr_cascade"),
-    ("kernels_extract.hip", "9k_compactE", "k_compact"),
+    ("kernels_fast.hip", "k_fast_cellsILi48ELb0EE", "k_fast_cells<48, false>"),
+    ("kernels_fast.hip", "k_fast_cellsILi64ELb0EE", "k_fast_cells<64, false>"),
+    ("kernels_orient_desc.hip", "k_orient_descILi2EE", "k_orient_desc<2>"),
+    ("kernels_pyramid.hip", "k_pyr_rowsILb0EE", "k_pyr_rows<false>"),
+    ("kernels_pyramid.hip", "k_pyr_rowsILb1EE", "k_pyr_rows<true>"),
+    ("kernels_pyramid.hip", "13k_pyr_cascadeE", "k_pyr_cascade"),
+    ("kernels_fast.hip", "9k_compactE", "k_compact"),
     ("kernels_octree.hip", "8k_octreeE", "k_octree"),
     ("kernels_match.hip", "14k_stereo_matchE", "k_stereo_match"),
     ("kernels_frame.hip", "19k_fisheye_2nn_batchE", "k_fisheye_2nn_batch"),
