@@ -2,8 +2,9 @@
 // uses - the division by a small wave-uniform divisor and the base of a pyramid level.  A helper that only one of those files
 // uses lives in that file.  Everything here is internal to the including file (an anonymous namespace; the 512-byte table
 // c_divMagic gets one copy per file that reads it): nothing links across files.
-// Device only: nothing includes this header except those three .hip files.  No MFMA anywhere in them: the path is integer /
-// bitwise.
+// Device only: nothing includes this header except those three .hip files and kernels_stereo.hip, the fourth reader of the
+// pyramid layout (level_ptr for k_stereo_match's SAD windows; it reads no c_divMagic and gets no copy of it).  No MFMA anywhere
+// in them: the path is integer / bitwise.
 #pragma once
 #include <algorithm>
 

@@ -228,7 +228,7 @@ size_t ft_octree_smem_bytes(int poolCap, bool compact = false);
 size_t ft_octree_hist_smem_bytes(int poolCap);
 int ft_octree_big_keys(int poolCap);
 
-// ---- kernel launchers (kernels_match.hip) ---------------------------------------------------
+// ---- kernel launchers (kernels_stereo.hip) --------------------------------------------------
 // A right keypoint as k_stereo_rowsort lays it down in row-bucket order: everything the left keypoint's scan needs in
 // one 48-byte entry, so the scan is one coalesced read instead of the chain index -> keypoint -> descriptor.
 struct __attribute__((aligned(16))) FtSortedR {
@@ -253,6 +253,38 @@ struct FtStereoArgs {
     int *leftOrder;                    // device [batch * capacity]: left keypoint indices ordered by (int)y (k_stereo_rowsort)
     int alignedLoads;                  // level-0 frames of both cameras are 4-byte aligned (base and stride): dword reads of image rows
 };
+int ft_launch_stereo_rowsort(hipStream_t st, const FtGeom &g, int batch, const FtStereoArgs &a);
+int ft_launch_stereo_match(hipStream_t st, const FtGeom &g, int batch, const uint8_t *const *l0L,
+                           const uint8_t *const *l0R, int l0pitchL, int l0pitchR, const uint8_t *pyrL,
+                           const uint8_t *pyrR, const FtStereoArgs &a);
+int ft_launch_stereo_median(hipStream_t st, int batch, const FtStereoArgs &a);
+
+// ---- kernel launchers (kernels_fisheye.hip; the launches of a tracked batch: ft_search.h) -------
+int ft_launch_fisheye(hipStream_t st, const uint8_t *descL, int nL, const uint8_t *descR, int nR, int *matches,
+                      int *best, int *second);
+struct FtFisheyeRig {
+    float cam1[8], cam2[8], precision, Rlr[9], tlr[3];
+    float sigma2[FT_MAX_LEVELS];
+};
+// KannalaBrandt8::TriangulateMatches for every left keypoint with a 2-NN match (matches[i] >= 0); rejected pairs
+// get matches[i] = -1; nMatches counts the survivors
+int ft_launch_fisheye_triangulate(hipStream_t st, const FtFisheyeRig &rig, const ft_keypoint *keysL, int nL,
+                                  const ft_keypoint *keysR, int *matches, float *depth, float *p3d, int *nMatches);
+int ft_launch_hamming_pairs(hipStream_t st, const uint8_t *a, const uint8_t *b, int n, int *dist);
+
+// ---- kernel launchers (kernels_frontend_io.hip) ---------------------------------------------
+// Frame upload of a small batch (latency mode): one kernel reads the frames from pinned host memory
+// and writes them as level 0 of the slot pyramids (row pitch `pitch`, `slotBytes` apart), and fills
+// the level-0 pointer table - instead of one DMA copy per frame plus one for the table.
+// Each frame is described by an entry of a table in pinned host memory that the kernel reads when it runs (so a captured
+// launch follows the frames of every replay): a frame the caller keeps in pinned memory is read where it is, any other
+// frame from the library's pinned staging copy.
+struct FtSrcEntry {
+    const uint8_t *ptr;
+    long long stride;
+};
+int ft_launch_upload(hipStream_t st, int batch, const FtSrcEntry *srcTab, int width, int height, uint8_t *slot0, int pitch,
+                     size_t slotBytes, const uint8_t **l0Table);
 // Result delivery of a small batch (latency mode): one kernel writes everything the host needs - keypoints and
 // descriptors of both cameras, mvuRight, mvDepth and the counters - straight into pinned host memory, instead of
 // eleven small copies through the DMA queue (each a few microseconds of work behind ~10 us of latency).
@@ -292,31 +324,3 @@ struct FtCountsArgs {
     int batch, nStreams;
 };
 int ft_launch_finish_counts(hipStream_t st, const FtCountsArgs &a);
-// Frame upload of a small batch (latency mode): one kernel reads the frames from pinned host memory
-// and writes them as level 0 of the slot pyramids (row pitch `pitch`, `slotBytes` apart), and fills
-// the level-0 pointer table - instead of one DMA copy per frame plus one for the table.
-// Each frame is described by an entry of a table in pinned host memory that the kernel reads when it runs (so a captured
-// launch follows the frames of every replay): a frame the caller keeps in pinned memory is read where it is, any other
-// frame from the library's pinned staging copy.
-struct FtSrcEntry {
-    const uint8_t *ptr;
-    long long stride;
-};
-int ft_launch_upload(hipStream_t st, int batch, const FtSrcEntry *srcTab, int width, int height, uint8_t *slot0, int pitch,
-                     size_t slotBytes, const uint8_t **l0Table);
-struct FtFisheyeRig {
-    float cam1[8], cam2[8], precision, Rlr[9], tlr[3];
-    float sigma2[FT_MAX_LEVELS];
-};
-// KannalaBrandt8::TriangulateMatches for every left keypoint with a 2-NN match (matches[i] >= 0); rejected pairs
-// get matches[i] = -1; nMatches counts the survivors
-int ft_launch_fisheye_triangulate(hipStream_t st, const FtFisheyeRig &rig, const ft_keypoint *keysL, int nL,
-                                  const ft_keypoint *keysR, int *matches, float *depth, float *p3d, int *nMatches);
-int ft_launch_stereo_match(hipStream_t st, const FtGeom &g, int batch, const uint8_t *const *l0L,
-                           const uint8_t *const *l0R, int l0pitchL, int l0pitchR, const uint8_t *pyrL,
-                           const uint8_t *pyrR, const FtStereoArgs &a);
-int ft_launch_stereo_median(hipStream_t st, int batch, const FtStereoArgs &a);
-int ft_launch_stereo_rowsort(hipStream_t st, const FtGeom &g, int batch, const FtStereoArgs &a);
-int ft_launch_fisheye(hipStream_t st, const uint8_t *descL, int nL, const uint8_t *descR, int nR, int *matches,
-                      int *best, int *second);
-int ft_launch_hamming_pairs(hipStream_t st, const uint8_t *a, const uint8_t *b, int n, int *dist);

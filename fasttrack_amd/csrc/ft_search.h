@@ -183,7 +183,7 @@ struct FtBindArgs {
 };
 // keypoints / descriptors of every frame into the reference's order, then the 2-NN + ratio matching of the lapping subsets
 int ft_launch_bind_fisheye_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxKp, const FtBindArgs &A);
-// KannalaBrandt8::TriangulateMatches for every ratio-test survivor of every frame (kernels_match.hip): keeps mvLeftToRightMatch
+// KannalaBrandt8::TriangulateMatches for every ratio-test survivor of every frame (kernels_fisheye.hip): keeps mvLeftToRightMatch
 // where the depth is > 0.0001, fills mvRightToLeftMatch, mvDepth, mvStereo3Dpoints and the frame's match count
 int ft_launch_fisheye_triangulate_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxKp, const FtBindArgs &A);
 int ft_launch_fill_claims_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxWords);

@@ -1,5 +1,5 @@
 // KannalaBrandt8::TriangulateMatches (reference src/CameraModels/KannalaBrandt8.cpp:306-372) on the device, shared by the
-// triangulation filter of two-camera frames (kernels_match.hip: k_fisheye_triangulate, k_fisheye_triangulate_batch) and by the
+// triangulation filter of two-camera frames (kernels_fisheye.hip: k_fisheye_triangulate, k_fisheye_triangulate_batch) and by the
 // epipolar constraint of ORBmatcher::SearchForTriangulation (kernels_triang.hip: KannalaBrandt8::epipolarConstrain, :216-220,
 // is TriangulateMatches(...) > 0.0001f).  The two cameras, KannalaBrandt8::precision and the pose (R12 row-major, t12) are
 // arguments: a rig has one pairing, a pair of two-camera keyframes four.

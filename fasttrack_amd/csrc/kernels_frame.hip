@@ -2,10 +2,9 @@
 //   k_build_grid(_batch)       Frame::AssignFeaturesToGrid (reference src/Frame.cc:409-440) as one CSR per octave
 //   k_frustum(_batch)          Frame::isInFrustum / isInFrustumChecks (src/Frame.cc:536-610, 1308-1382) + MapPoint::PredictScale
 //   k_fill_*                   the start values of a claim iteration
-//   k_lap_gather_batch, k_fisheye_2nn_batch   two-camera frames of a batch from what two extractors left in HBM: the reference's
-//                              keypoint order (src/ORBextractor.cc:1466-1487), Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1231-1255)
 //   k_gather_batch, k_deliver_blocks, k_deliver_batch   pinned host memory <-> device, one launch per direction
-// The searches themselves: kernels_search.hip, kernels_search_rows.hip, kernels_resolve.hip.
+// The searches themselves: kernels_search.hip, kernels_search_rows.hip, kernels_resolve.hip.  The two-camera frames of a batch
+// from what two extractors left in HBM (ft_tracked_batch_bind_fisheye): kernels_fisheye.hip.
 #include <algorithm>
 
 #include "search_dev.h"
@@ -176,125 +175,6 @@ __global__ __launch_bounds__(256) void k_fill_claims_batch(const FtBatchJob *__r
         for (int i = t; i < 2 * J.nPoints; i += T) cache[(size_t)i * (FT_CACHE_CAP + 1)] = ~0ull;
 }
 
-// ---- two-camera frames of a batch straight from what two extractors left in HBM (ft_tracked_batch_bind_fisheye) ----
-// Step 1, workgroup (camera, frame): the keypoints and descriptors of the extractor's slot into the frame's arrays in the
-// REFERENCE's order - ORBextractor::operator() fills keypoints inside the lapping area from the back and the others from the
-// front (src/ORBextractor.cc:1466-1487; assembleOutputs, extractor.cpp, does the same for the host copies) - a stable
-// partition by ranks from ballots; also: the camera's match table = -1, and the number of keypoints outside the lapping
-// area (monoLeft / monoRight, src/Frame.cc:1144-1147) for step 2.
-__global__ __launch_bounds__(256) void k_lap_gather_batch(const FtBatchJob *__restrict__ jobs, Rebase rb, FtBindArgs A) {
-    const int cam = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const FtDevFrame &F = jobs[f].F;
-    const int slot = (cam == 0 ? A.slot0L : A.slot0R) + f;
-    const int n = cam == 0 ? F.Nleft : F.N - F.Nleft;
-    const ft_keypoint *src = (cam == 0 ? A.keysL : A.keysR) + (size_t)slot * (cam == 0 ? A.strideL : A.strideR);
-    const uint4 *srcD = (const uint4 *)((cam == 0 ? A.descL : A.descR) + (size_t)slot * (cam == 0 ? A.strideL : A.strideR) * 32);
-    ft_keypoint *dst = (ft_keypoint *)rb(cam == 0 ? F.keys : F.keysR);
-    uint4 *dstD = (uint4 *)(rb((uint8_t *)F.desc) + (cam == 0 ? 0 : (size_t)F.Nleft * 32));
-    int *tab = (int *)rb(cam == 0 ? F.l2r : F.r2l);
-    const float lap0 = (float)(cam == 0 ? A.lapL0 : A.lapR0), lap1 = (float)(cam == 0 ? A.lapL1 : A.lapR1);
-    __shared__ int wLap[4];
-    int lapBefore = 0;  // lapping-area keypoints in front of this chunk
-    for (int base = 0; base < n; base += 256) {
-        const int i = base + tid;
-        ft_keypoint kp;
-        bool inLap = false;
-        if (i < n) {
-            kp = src[i];
-            inLap = kp.x >= lap0 && kp.x <= lap1;
-        }
-        const unsigned long long b = __ballot(inLap);
-        if (lane == 0) wLap[wave] = __popcll(b);
-        __syncthreads();
-        int before = lapBefore;
-        for (int w = 0; w < wave; w++) before += wLap[w];
-        const int chunkLap = wLap[0] + wLap[1] + wLap[2] + wLap[3];
-        __syncthreads();
-        if (i < n) {
-            const int rankLap = before + __popcll(b & ((1ull << lane) - 1ull));
-            const int d = inLap ? n - 1 - rankLap : i - rankLap;
-            dst[d] = kp;
-            dstD[2 * (size_t)d] = srcD[2 * (size_t)i];
-            dstD[2 * (size_t)d + 1] = srcD[2 * (size_t)i + 1];
-            tab[i] = -1;
-        }
-        lapBefore += chunkLap;
-    }
-    if (tid == 0) {
-        A.mono[2 * f + cam] = n - lapBefore;
-        if (cam == 0 && A.nMatches) A.nMatches[f] = 0;
-    }
-}
-
-// Step 2: the matching part of Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1231-1255; the seam of the reference's
-// launchFisheyeStereoMatchKernel, include/Kernels/KernelController.h:38) for every frame of the batch: BFMatcher(NORM_HAMMING)
-// .knnMatch(k = 2) of the left lapping subset [monoLeft, Nleft) against the right one + Lowe's ratio 0.7, written as
-// mvLeftToRightMatch / mvRightToLeftMatch (a right keypoint matched by several left ones keeps the last = largest index, as the
-// reference's loop does).  A wave takes FE_Q queries: a lane holds one train descriptor of the current 64 in registers and
-// meets the queries through LDS broadcasts, so a train descriptor is fetched once per FE_Q queries (the one-query-per-wave
-// form of k_fisheye_2nn reads the whole train set per query: 128 MB of L2 traffic per 2000 x 2000 frame); keys
-// (distance << 20 | train index), two smallest per lane and query, one wave reduction per query at the end.
-#define FE_Q 16
-// fillR2l = 0: the triangulation filter follows (k_fisheye_triangulate_batch), which writes mvRightToLeftMatch for the pairs it keeps
-__global__ __launch_bounds__(256) void k_fisheye_2nn_batch(const FtBatchJob *__restrict__ jobs, Rebase rb, const int *__restrict__ mono,
-                                                           int fillR2l) {
-    const int f = blockIdx.y, lane = threadIdx.x & 63, wave = wave_index();
-    const FtDevFrame &F = jobs[f].F;
-    const int monoL = mono[2 * f], monoR = mono[2 * f + 1];
-    const int nQ = F.Nleft - monoL, nT = (F.N - F.Nleft) - monoR;
-    const int q0 = (blockIdx.x * 4 + wave) * FE_Q;
-    if (q0 >= nQ) return;
-    const uint8_t *desc = rb(F.desc);
-    const uint4 *qd = (const uint4 *)(desc + (size_t)(monoL + q0) * 32);
-    const uint4 *td = (const uint4 *)(desc + (size_t)(F.Nleft + monoR) * 32);
-    __shared__ uint4 qs[4][FE_Q * 2];
-    const int nq = min(FE_Q, nQ - q0);
-    if (lane < 2 * nq) qs[wave][lane] = qd[lane];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    unsigned k0[FE_Q], k1[FE_Q];
-#pragma unroll
-    for (int q = 0; q < FE_Q; q++) k0[q] = k1[q] = 0xffffffffu;
-    // (the next train descriptor is requested before the current one is compared with the sixteen queries: 320 vector
-    // instructions cover its round trip, where two waves per SIMD - 175 registers - could not)
-    uint4 an = make_uint4(0, 0, 0, 0), bn = an;
-    if (lane < nT) {
-        an = td[2 * (size_t)lane];
-        bn = td[2 * (size_t)lane + 1];
-    }
-    for (int j = lane; j < nT; j += 64) {
-        const uint4 a = an, b = bn;
-        if (j + 64 < nT) {
-            an = td[2 * (size_t)(j + 64)];
-            bn = td[2 * (size_t)(j + 64) + 1];
-        }
-#pragma unroll
-        for (int q = 0; q < FE_Q; q++) {
-            const uint4 x = qs[wave][2 * q], y = qs[wave][2 * q + 1];  // (same address in every lane: a broadcast)
-            const unsigned d = __popc(a.x ^ x.x) + __popc(a.y ^ x.y) + __popc(a.z ^ x.z) + __popc(a.w ^ x.w) + __popc(b.x ^ y.x) +
-                               __popc(b.y ^ y.y) + __popc(b.z ^ y.z) + __popc(b.w ^ y.w);
-            const unsigned key = (d << 20) | (unsigned)j;
-            k1[q] = min(k1[q], max(k0[q], key));
-            k0[q] = min(k0[q], key);
-        }
-    }
-    int *l2r = (int *)rb(F.l2r), *r2l = (int *)rb(F.r2l);
-#pragma unroll
-    for (int q = 0; q < FE_Q; q++) {
-        const unsigned m0 = wave_min_u32(k0[q]);
-        const unsigned cand = (k0[q] == m0) ? k1[q] : k0[q];
-        const unsigned m1 = wave_min_u32(cand);
-        if (lane == 0 && q < nq) {
-            const int d0 = (int)(m0 >> 20), d1 = (int)(m1 >> 20);
-            if (nT >= 2 && (double)(float)d0 < (double)(float)d1 * 0.7) {
-                const int t = monoR + (int)(m0 & 0xfffffu), qi = monoL + q0 + q;
-                l2r[qi] = t;
-                if (fillR2l) atomicMax(&r2l[t], qi);
-            }
-        }
-    }
-}
-
 // Result delivery of a batch: record r (blockIdx.y) = one block of dwords written into pinned host memory; src[parity] lets a
 // record follow the result buffer of the pass that ran last.
 // The copy is bound by PCIe (a few hundred workgroups' stores in flight saturate it), so a record gets few workgroups that move
@@ -428,15 +308,6 @@ int ft_launch_fill_claims_batch(hipStream_t st, void *arena, const FtBatchJob *j
 int ft_launch_deliver_batch(hipStream_t st, const FtDeliverRec *recs, int nRecs, int maxWords, int parity) {
     if (nRecs <= 0 || maxWords <= 0) return FT_OK;
     hipLaunchKernelGGL(k_deliver_batch, dim3(std::max(1, std::min(FT_DELIVER_BLOCKS, (maxWords + 1023) / 1024)), nRecs), dim3(256), 0, st, recs, parity);
-    FT_HIP(hipGetLastError());
-    return FT_OK;
-}
-
-int ft_launch_bind_fisheye_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxKp, const FtBindArgs &A) {
-    if (nFrames <= 0) return FT_OK;
-    hipLaunchKernelGGL(k_lap_gather_batch, dim3(2, nFrames), dim3(256), 0, st, jobs, rebase_of(arena), A);
-    hipLaunchKernelGGL(k_fisheye_2nn_batch, dim3((maxKp + 4 * FE_Q - 1) / (4 * FE_Q), nFrames), dim3(256), 0, st, jobs, rebase_of(arena),
-                       (const int *)A.mono, A.triangulate ? 0 : 1);
     FT_HIP(hipGetLastError());
     return FT_OK;
 }

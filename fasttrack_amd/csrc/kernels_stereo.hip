@@ -1,26 +1,13 @@
-// HIP kernels of the Hamming matchers for gfx950 (wave64): 256-bit descriptors as 4 x uint64 with
-// __popcll (k_stereo_match: 8 x v_bcnt in one chain), minima on packed (distance, index) keys so ties
-// resolve exactly like the reference's sequential "dist < bestDist" scans.
-//   k_stereo_match   Frame::ComputeStereoMatches  (reference src/Frame.cc:835-989)
-//   k_stereo_median  the 1.5*1.4*median SAD cut    (src/Frame.cc:991-1004)
-//   k_fisheye_2nn    BFMatcher knnMatch(k=2)+ratio (src/Frame.cc:1231-1255)
-//   k_hamming_pairs  ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:2256-2272)
-#include "ft_internal.h"
-#include "ft_search.h"
-#include "kb8_triangulate.h"
-#include "wave_ops.h"
+// HIP kernels of the rectified stereo matcher for gfx950 (wave64): 256-bit descriptors as 8 x v_bcnt in one chain, minima on
+// packed (distance, index) keys so ties resolve exactly like the reference's sequential "dist < bestDist" scans.
+//   k_stereo_rowsort  the row buckets vRowIndices  (reference src/Frame.cc:845-863), and the left keypoints by row
+//   k_stereo_match    Frame::ComputeStereoMatches  (src/Frame.cc:835-989)
+//   k_stereo_median   the 1.5*1.4*median SAD cut   (src/Frame.cc:991-1004)
+// k_stereo_match reads the pyramid the extractor left in HBM: level_ptr is extract_dev.h's (the fourth reader of that layout).
+// Host side: stereo_frontend.cpp.
+#include "extract_dev.h"
 
 namespace {
-
-__device__ __forceinline__ const uint8_t *level_ptr(const FtGeom &g, int level, int slot, const uint8_t *const *l0,
-                                                    int l0pitch, const uint8_t *pyr, int &pitch) {
-    if (level == 0) {
-        pitch = l0pitch;
-        return l0[slot];
-    }
-    pitch = g.lv[level].pitch;
-    return pyr + (size_t)slot * g.pyrPerSlot + g.lv[level].off;
-}
 
 // ---- k_stereo_match: one workgroup per group of ST_G = 64 left keypoints taken in row order -----------------------------
 // k_stereo_rowsort leaves the right keypoints bucketed by (int)y (`sorted`, `rowStart`) and the left keypoint indices
@@ -546,266 +533,11 @@ __global__ __launch_bounds__(64) void k_stereo_median(FtStereoArgs a) {
     if (lane == 0) a.nMatches[slot] = total - removed;
 }
 
-// Brute-force 2-NN: one wave per query, lanes stride over the train set; the two smallest
-// (distance, index) keys of the wave are the reference's (best, second) with earlier index first.
-__global__ __launch_bounds__(256) void k_fisheye_2nn(const uint8_t *descL, int nL, const uint8_t *descR, int nR,
-                                                     int *matches, int *bestOut, int *secondOut) {
-    const int lane = threadIdx.x & 63, wave = wave_index();
-    const int i = blockIdx.x * 4 + wave;
-    if (i >= nL) return;
-    unsigned long long q[4];
-    {
-        const unsigned long long *p = (const unsigned long long *)(descL + (size_t)i * 32);
-        q[0] = p[0]; q[1] = p[1]; q[2] = p[2]; q[3] = p[3];
-    }
-    unsigned k0 = 0xffffffffu, k1 = 0xffffffffu;  // two smallest keys seen by this lane
-    for (int j = lane; j < nR; j += 64) {
-        const unsigned key = ((unsigned)hamming256(q, (const unsigned long long *)(descR + (size_t)j * 32)) << 20) | (unsigned)j;
-        if (key < k0) { k1 = k0; k0 = key; }
-        else if (key < k1) k1 = key;
-    }
-    const unsigned m0 = wave_min_u32(k0);
-    // second smallest overall: lanes whose k0 was the global minimum contribute their k1 instead
-    const unsigned cand = (k0 == m0) ? k1 : k0;
-    const unsigned m1 = wave_min_u32(cand);
-    if (lane == 0) {
-        const int d0 = (int)(m0 >> 20), d1 = (int)(m1 >> 20);
-        int match = -1;
-        if (nR >= 2 && (double)(float)d0 < (double)(float)d1 * 0.7) match = (int)(m0 & 0xfffffu);
-        matches[i] = match;
-        if (bestOut) bestOut[i] = nR >= 1 ? d0 : -1;
-        if (secondOut) secondOut[i] = nR >= 2 ? d1 : -1;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_hamming_pairs(const uint8_t *a, const uint8_t *b, int n, int *dist) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long *pa = (const unsigned long long *)(a + (size_t)i * 32);
-    unsigned long long q[4] = {pa[0], pa[1], pa[2], pa[3]};
-    dist[i] = hamming256(q, (const unsigned long long *)(b + (size_t)i * 32));
-}
-
-// KannalaBrandt8::TriangulateMatches (kb8_triangulate.h) for the pairs that passed the ratio test: one thread per left keypoint.
-__global__ __launch_bounds__(64) void k_fisheye_triangulate(FtFisheyeRig rig, const ft_keypoint *keysL, int nL, const ft_keypoint *keysR,
-                                                           int *matches, float *depth, float *p3d, int *nMatches) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= nL) return;
-    const int j = matches[i];
-    float d = -1.0f, p[3] = {0.f, 0.f, 0.f};
-    int m = -1;
-    if (j >= 0) {
-        const ft_keypoint a = keysL[i], b = keysR[j];
-        const float z = kb8_triangulate_matches(rig.cam1, rig.cam2, rig.precision, rig.Rlr, rig.tlr, a.x, a.y, b.x, b.y, rig.sigma2[a.octave], rig.sigma2[b.octave], p);
-        if (z > 0.0001f) {  // Frame.cc:1263
-            d = z;
-            m = j;
-            atomicAdd(nMatches, 1);
-        } else {
-            p[0] = p[1] = p[2] = 0.f;
-        }
-    }
-    matches[i] = m;
-    depth[i] = d;
-    p3d[3 * i] = p[0];
-    p3d[3 * i + 1] = p[1];
-    p3d[3 * i + 2] = p[2];
-}
-
-// The same for every frame of a tracked batch (blockIdx.y = frame): the pairs k_fisheye_2nn_batch left in mvLeftToRightMatch
-// (right-camera indices) are triangulated; a pair that fails loses its entry, a pair that stays enters mvRightToLeftMatch (the
-// largest left index per right keypoint = the last writer of the reference's loop, src/Frame.cc:1262) and mvDepth / mvStereo3Dpoints
-__global__ __launch_bounds__(256) void k_fisheye_triangulate_batch(const FtBatchJob *__restrict__ jobs, Rebase rb, FtBindArgs A) {
-    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    const FtDevFrame &F = jobs[f].F;
-    if (i >= F.Nleft) return;
-    int *l2r = (int *)rb(F.l2r), *r2l = (int *)rb(F.r2l);
-    const int j = l2r[i];
-    float d = -1.0f, p[3] = {0.f, 0.f, 0.f};
-    if (j >= 0) {
-        const ft_keypoint a = rb(F.keys)[i], b = rb(F.keysR)[j];
-        const float z = kb8_triangulate_matches(A.rig.cam1, A.rig.cam2, A.rig.precision, A.rig.Rlr, A.rig.tlr, a.x, a.y, b.x, b.y, A.rig.sigma2[a.octave], A.rig.sigma2[b.octave], p);
-        if (z > 0.0001f) {  // Frame.cc:1263
-            d = z;
-            atomicMax(&r2l[j], i);
-            atomicAdd(&A.nMatches[f], 1);
-        } else {
-            p[0] = p[1] = p[2] = 0.f;
-            l2r[i] = -1;
-        }
-    }
-    if (A.depth) {
-        float *dep = rb(A.depth[f]), *pp = rb(A.p3d[f]);
-        dep[i] = d;
-        pp[3 * i] = p[0];
-        pp[3 * i + 1] = p[1];
-        pp[3 * i + 2] = p[2];
-    }
-}
-
 }  // namespace
 
-int ft_launch_fisheye_triangulate_batch(hipStream_t st, void *arena, const FtBatchJob *jobs, int nFrames, int maxKp, const FtBindArgs &A) {
-    if (nFrames <= 0 || maxKp <= 0) return FT_OK;
-    const Rebase rb{(uint8_t *)arena, (unsigned long long)(uintptr_t)arena};
-    hipLaunchKernelGGL(k_fisheye_triangulate_batch, dim3((maxKp + 255) / 256, nFrames), dim3(256), 0, st, jobs, rb, A);
-    FT_HIP(hipGetLastError());
-    return FT_OK;
-}
-
-namespace {
-// grid (DL_BLOCKS, batch): the blocks of an image share the rows of its six result arrays dword by dword (every record
-// size is a multiple of four bytes); the stores go over the host link, the counters with them
-#define DL_BLOCKS 24
-__global__ __launch_bounds__(256) void k_deliver(FtDeliverArgs a) {
-    const int slot = blockIdx.y;
-    const int nl = a.nL[slot], nr = a.nR ? a.nR[slot] : 0;  // one camera only: the right-hand pointers are null
-    const int t = blockIdx.x * 256 + threadIdx.x, T = DL_BLOCKS * 256;
-    auto rows = [&](const void *src, void *dst, int recBytes, int n) {
-        if (!dst || n <= 0) return;
-        const unsigned *s = (const unsigned *)((const uint8_t *)src + (size_t)slot * a.srcStride * recBytes);
-        unsigned *d = (unsigned *)((uint8_t *)dst + (size_t)slot * a.dstStride * recBytes);
-        const int words = n * (recBytes >> 2);
-        for (int i = t; i < words; i += T) d[i] = s[i];
-    };
-    rows(a.keysL, a.oKeysL, (int)sizeof(ft_keypoint), nl);
-    rows(a.descL, a.oDescL, 32, nl);
-    rows(a.uright, a.oUright, 4, nl);
-    rows(a.depth, a.oDepth, 4, nl);
-    rows(a.keysR, a.oKeysR, (int)sizeof(ft_keypoint), nr);
-    rows(a.descR, a.oDescR, 32, nr);
-    if (t == 0) {
-        a.oNL[slot] = nl;
-        if (a.oNR) a.oNR[slot] = nr;
-        if (a.oNMatches) a.oNMatches[slot] = a.nMatches[slot];
-        if (slot == 0) {
-            *a.oOverflowL = *a.overflowL;
-            if (a.oOverflowR) *a.oOverflowR = *a.overflowR;
-        }
-    }
-}
-}  // namespace
-
-namespace {
-// The results of ft_extract_batch in the order ORBextractor::operator() returns them (src/ORBextractor.cc:1466-1487: keypoints
-// outside the lapping area fill the output from the front, those inside it from the back), written straight into the caller's
-// arrays in pinned host memory: a workgroup per image, the position of a keypoint from a running count of the lapping-area
-// keypoints in front of it (ballots, wave totals through LDS).  Replaces the copy of whole rows into the library's staging and
-// the host's pass over them (ft_extract_batch: 2 x 15 MB per 128 two-camera frames of 2 000 features, through the context's
-// host threads).  An image with more keypoints than the caller's rows hold is left alone (the host reports FT_ERR_CAPACITY).
-__global__ __launch_bounds__(256) void k_deliver_ordered(FtOrderedArgs a) {
-    const int slot = a.b0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = a.nSel[slot];
-    __shared__ int wcnt[2][4];
-    if (n > a.capacity) {
-        if (tid == 0) a.oMono[slot] = 0;
-        return;
-    }
-    const unsigned *src = (const unsigned *)(a.keys + (size_t)slot * a.srcStride);
-    const uint4 *sd = (const uint4 *)(a.desc + (size_t)slot * a.srcStride * 32);
-    unsigned *dk = a.oKeys ? (unsigned *)(a.oKeys + (size_t)slot * a.capacity) : nullptr;
-    uint4 *dd = a.oDesc ? (uint4 *)(a.oDesc + (size_t)slot * a.capacity * 32) : nullptr;
-    constexpr int W = (int)sizeof(ft_keypoint) / 4;
-    int lapBefore = 0;
-    for (int base = 0, r = 0; base < n; base += 256, r ^= 1) {  // (uniform)
-        const int i = base + tid;
-        const bool real = i < n;
-        unsigned kw[W];
-#pragma unroll
-        for (int k = 0; k < W; k++) kw[k] = real ? src[(size_t)i * W + k] : 0u;
-        const float x = __uint_as_float(kw[0]);  // ft_keypoint::x is the first field
-        const bool inLap = real && x >= a.lap0 && x <= a.lap1;
-        const unsigned long long bal = __ballot(inLap);
-        if (lane == 0) wcnt[r][wave] = __popcll(bal);
-        __syncthreads();  // (two buffers: the next round's writes cannot pass a reader of this one)
-        int below = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            below += w < wave ? wcnt[r][w] : 0;
-            total += wcnt[r][w];
-        }
-        if (real) {
-            const int rankLap = lapBefore + below + __popcll(bal & ((1ull << lane) - 1ull));
-            const int dst = inLap ? n - 1 - rankLap : i - rankLap;
-            if (dk) {
-#pragma unroll
-                for (int k = 0; k < W; k++) dk[(size_t)dst * W + k] = kw[k];
-            }
-            if (dd) {
-                dd[2 * (size_t)dst] = sd[2 * (size_t)i];
-                dd[2 * (size_t)dst + 1] = sd[2 * (size_t)i + 1];
-            }
-        }
-        lapBefore += total;
-    }
-    if (tid == 0) a.oMono[slot] = n - lapBefore;
-}
-
-__global__ __launch_bounds__(256) void k_upload(const FtSrcEntry *srcTab, int width, int height, uint8_t *slot0, int pitch,
-                                                size_t slotBytes, const uint8_t **l0Table) {
-    const int slot = blockIdx.y;
-    const FtSrcEntry e = srcTab[slot];  // (pinned host memory, written by the host just before the launch or replay)
-    const uint8_t *src = e.ptr;
-    const size_t sstride = (size_t)e.stride;
-    uint8_t *dst = slot0 + (size_t)slot * slotBytes;
-    const int t = blockIdx.x * 256 + threadIdx.x, T = gridDim.x * 256;
-    if ((width & 3) == 0 && (((uintptr_t)src | sstride) & 3) == 0) {  // dword columns (the slot pitch is a multiple of 64 bytes)
-        const int wq = width >> 2, n = wq * height;
-        for (int i = t; i < n; i += T) {
-            const int y = i / wq, x = i - y * wq;
-            ((unsigned *)(dst + (size_t)y * pitch))[x] = ((const unsigned *)(src + (size_t)y * sstride))[x];
-        }
-    } else {
-        const int n = width * height;
-        for (int i = t; i < n; i += T) {
-            const int y = i / width, x = i - y * width;
-            dst[(size_t)y * pitch + x] = src[(size_t)y * sstride + x];
-        }
-    }
-    if (t == 0) l0Table[slot] = dst;
-}
-}  // namespace
-
-int ft_launch_upload(hipStream_t st, int batch, const FtSrcEntry *srcTab, int width, int height, uint8_t *slot0, int pitch,
-                     size_t slotBytes, const uint8_t **l0Table) {
-    hipLaunchKernelGGL(k_upload, dim3(48, batch), dim3(256), 0, st, srcTab, width, height, slot0, pitch, slotBytes, l0Table);
-    FT_HIP(hipGetLastError());
-    return FT_OK;
-}
-
-namespace {
-// the counters the host reads at the end of a wide batch - per-image totals, the overflow flag, the demand of the octree tiers
-// behind k_octree (reset here for the next batch) - written to pinned host memory by ONE small kernel: they were six or seven
-// 4-byte copies and two fills through the DMA queue, ~18 us of link latency each, one after the other at the tail of every
-// ft_extract_batch / front-end batch
-__global__ __launch_bounds__(256) void k_finish_counts(FtCountsArgs a) {
-    for (int i = threadIdx.x; i < a.batch; i += 256) a.oNSel[i] = a.nSel[i];
-    if (threadIdx.x == 0) *a.oOverflow = *a.overflow;
-    if (a.bigCount && (int)threadIdx.x < a.nStreams) {
-        const int k = threadIdx.x;
-        a.oHist[k] = a.bigCount[4 * k + 2];
-        a.oBig[k] = a.bigCount[4 * k + 3];
-        a.bigCount[4 * k + 2] = 0;
-        a.bigCount[4 * k + 3] = 0;
-    }
-}
-}  // namespace
-
-int ft_launch_finish_counts(hipStream_t st, const FtCountsArgs &a) {
-    hipLaunchKernelGGL(k_finish_counts, dim3(1), dim3(256), 0, st, a);
-    FT_HIP(hipGetLastError());
-    return FT_OK;
-}
-
-int ft_launch_deliver_ordered(hipStream_t st, int nb, const FtOrderedArgs &a) {
-    if (nb <= 0) return FT_OK;
-    hipLaunchKernelGGL(k_deliver_ordered, dim3(nb), dim3(256), 0, st, a);
-    FT_HIP(hipGetLastError());
-    return FT_OK;
-}
-
-int ft_launch_deliver(hipStream_t st, int batch, const FtDeliverArgs &a) {
-    hipLaunchKernelGGL(k_deliver, dim3(DL_BLOCKS, batch), dim3(256), 0, st, a);
+int ft_launch_stereo_rowsort(hipStream_t st, const FtGeom &g, int batch, const FtStereoArgs &a) {
+    for (int rep = ft_debug_repeat("rowsort"); rep > 0; rep--)
+    hipLaunchKernelGGL(k_stereo_rowsort, dim3(batch), dim3(256), (size_t)2 * (g.lv[0].h + 1) * sizeof(int), st, g, a);
     FT_HIP(hipGetLastError());
     return FT_OK;
 }
@@ -821,38 +553,8 @@ int ft_launch_stereo_match(hipStream_t st, const FtGeom &g, int batch, const uin
     return FT_OK;
 }
 
-int ft_launch_stereo_rowsort(hipStream_t st, const FtGeom &g, int batch, const FtStereoArgs &a) {
-    for (int rep = ft_debug_repeat("rowsort"); rep > 0; rep--)
-    hipLaunchKernelGGL(k_stereo_rowsort, dim3(batch), dim3(256), (size_t)2 * (g.lv[0].h + 1) * sizeof(int), st, g, a);
-    FT_HIP(hipGetLastError());
-    return FT_OK;
-}
-
 int ft_launch_stereo_median(hipStream_t st, int batch, const FtStereoArgs &a) {
     hipLaunchKernelGGL(k_stereo_median, dim3(batch), dim3(64), 0, st, a);
-    FT_HIP(hipGetLastError());
-    return FT_OK;
-}
-
-int ft_launch_fisheye(hipStream_t st, const uint8_t *descL, int nL, const uint8_t *descR, int nR, int *matches,
-                      int *best, int *second) {
-    if (nL <= 0) return FT_OK;
-    hipLaunchKernelGGL(k_fisheye_2nn, dim3((nL + 3) / 4), dim3(256), 0, st, descL, nL, descR, nR, matches, best, second);
-    FT_HIP(hipGetLastError());
-    return FT_OK;
-}
-
-int ft_launch_hamming_pairs(hipStream_t st, const uint8_t *a, const uint8_t *b, int n, int *dist) {
-    if (n <= 0) return FT_OK;
-    hipLaunchKernelGGL(k_hamming_pairs, dim3((n + 255) / 256), dim3(256), 0, st, a, b, n, dist);
-    FT_HIP(hipGetLastError());
-    return FT_OK;
-}
-
-int ft_launch_fisheye_triangulate(hipStream_t st, const FtFisheyeRig &rig, const ft_keypoint *keysL, int nL,
-                                  const ft_keypoint *keysR, int *matches, float *depth, float *p3d, int *nMatches) {
-    if (nL <= 0) return FT_OK;
-    hipLaunchKernelGGL(k_fisheye_triangulate, dim3((nL + 63) / 64), dim3(64), 0, st, rig, keysL, nL, keysR, matches, depth, p3d, nMatches);
     FT_HIP(hipGetLastError());
     return FT_OK;
 }

@@ -1,6 +1,6 @@
 // Host side of the projection searches, shared by the translation units of the entry-point families (search_view.cpp,
 // tracked_frame.cpp, init_search.cpp, reloc_search.cpp, triang_search.cpp, fuse_search.cpp, sim3_search.cpp, tracked_batch.cpp; bow.cpp, bow_kf_search.cpp,
-// distinct_desc.cpp and matcher.cpp for the call skeleton at the end: Arena, CallScope): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
+// distinct_desc.cpp and fisheye_match.cpp for the call skeleton at the end: Arena, CallScope): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
 // (reference include/Kernels/KernelController.h:40-46) together with the acceptance loops the reference keeps in the caller
 // (src/ORBmatcher.cc:241-308, 2013-2081).  Windowing, level/box tests and every Hamming distance run on the device
 // (kernels_search*.hip, kernels_resolve.hip, kernels_frame.hip); the host only marshals arrays, drives the fixed-point passes and
@@ -694,7 +694,7 @@ inline int ensureInitArena(ft_tracked_frame *tf, size_t devBytes, size_t pinByte
     return FT_OK;
 }
 
-// ---- a one-shot call on an arena and its pinned mirror: the keyframe matchers, bow.cpp, matcher.cpp's fisheye / distance calls, search_view.cpp's queries ----
+// ---- a one-shot call on an arena and its pinned mirror: the keyframe matchers, bow.cpp, fisheye_match.cpp's fisheye / distance calls, search_view.cpp's queries ----
 // The event timer of a stand-alone call, destroyed with the call's scope.  (FtEventTimer itself has no destructor: extractors,
 // tracked frames and batches keep theirs for their lifetime and destroy it where they free their streams.)
 struct CallEventTimer {

@@ -560,6 +560,19 @@ def test_tracked_batch_bind_with_triangulation_equals_oracle_fisheye_stereo(ctx)
         m = ob.fisheye_match(rL[f][1][rL[f][2]:], rR[f][1][rR[f][2]:])["matches"]
         dropped += int((m >= 0).sum()) - n
     assert kept > 5 * B and dropped > 0      # the filter keeps pairs and rejects pairs
+    # the same bind by a caller that takes no mvDepth / mvStereo3Dpoints (k_fisheye_triangulate_batch without depth outputs): the
+    # filtered tables and the counts alone, equal to the ones above
+    import ctypes as C
+    from fasttrack_amd import _capi
+    arr, _ = tb.prepare_frames(views)
+    l2r = [np.full(len(wf[0]), -1, np.int32) for wf in want]
+    r2l = [np.full(len(wf[1]), -1, np.int32) for wf in want]
+    nst, ls2 = np.zeros(B, np.int32), np.ascontiguousarray(sig2, np.float32)
+    pl, pr = (C.c_void_p * B)(*[orb.ptr(a) for a in l2r]), (C.c_void_p * B)(*[orb.ptr(a) for a in r2l])
+    _capi.check(_capi.lib().ft_tracked_batch_bind_fisheye_slots(tb._h, exL._h, exR._h, 0, 0, B, lap[0], lap[1], lap[0], lap[1], arr,
+                                                                C.byref(grig), orb.ptr(ls2), pl, pr, None, None, orb.ptr(nst)))
+    for f in range(B):
+        assert np.array_equal(l2r[f], want[f][0]) and np.array_equal(r2l[f], want[f][1]) and nst[f] == want[f][4], f
     for o in (tb, exL, exR):
         o.close()
 

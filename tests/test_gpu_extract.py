@@ -179,6 +179,24 @@ def test_wide_batch_delivered_in_order_into_pinned_arrays(ctx):
     assert (kps.view(np.uint8) == 0xAB).all()
 
 
+def test_wide_batch_counts_without_octree_tiers(ctx):
+    """k_finish_counts of an extractor with no tier behind k_octree (options oct_hist = 0 and oct_big = 0, taken when the extractor
+    is made): the kernel gets no demand counters and delivers the per-image totals and the overflow flag alone.  Nine images -
+    beyond latency mode, where k_deliver carries the counters - into pageable arrays, against the oracle."""
+    w, h, nf, B = 320, 240, 500, 9
+    imgs = [synth.make_image(w, h, seed=400 + b) for b in range(B)]
+    with ctx.options(oct_hist=0, oct_big=0):
+        ex = orb.ORBextractor(ctx, nf, 1.2, 8, 20, 7, w, h, max_batch=B)
+    f0 = _calls(ctx, "extract.device_octree_fallbacks")
+    res = ex.extract_batch(imgs)
+    assert _calls(ctx, "extract.device_octree_fallbacks") == f0  # every level within the first tier: the device octree's counts
+    oex = ob.Extractor(nf)
+    for b in range(B):
+        ok, od, _ = oex.extract(imgs[b])
+        _check_same(res[b][0], res[b][1], ok, od)
+    ex.close()
+
+
 def test_edge_images(ctx):
     w, h, nf = 640, 480, 1000
     ex = orb.ORBextractor(ctx, nf, 1.2, 8, 20, 7, w, h)

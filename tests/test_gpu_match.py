@@ -105,6 +105,30 @@ def test_stereo_frontend_fused(ctx, w, h, nf, B):
             assert np.array_equal(out["uright"], o["uright"]) and np.array_equal(out["depth"], o["depth"])
 
 
+def test_stereo_frontend_small_batch_on_two_extractors(ctx):
+    """latency mode with the cameras on their own extractors (option paired = 0, taken when the front end is made): k_deliver
+    reads the right camera's rows, counts and overflow flag from the right extractor's arrays, not from the upper half of the
+    left one's; pinned outputs (the captured graph) and pageable ones (the staging), against the oracle"""
+    w, h, nf, B = 320, 240, 300, 2
+    intr = synth.intrinsics(w, h)
+    with ctx.options(paired=0):
+        fes = [orb.StereoFrontend(ctx, nf, 1.2, 8, 20, 7, w, h, B, intr["mbf"], intr["mb"], pinned_outputs=p) for p in (True, False)]
+    pairs = [synth.make_stereo_pair(w, h, 240 + b) for b in range(B)]
+    for fe in fes:
+        for _ in range(2):  # (the second call of the pinned front end replays the graph)
+            outs = fe.process([p[0] for p in pairs], [p[1] for p in pairs])
+            for b in range(B):
+                oL, oR = ob.Extractor(nf), ob.Extractor(nf)
+                kL, dL, _ = oL.extract(pairs[b][0])
+                kR, dR, _ = oR.extract(pairs[b][1])
+                o = ob.stereo_match(oL, oR, kL, kR, dL, dR, intr["mbf"], intr["mb"])
+                out = outs[b]
+                assert np.array_equal(out["keysL"], kL) and np.array_equal(out["keysR"], kR)
+                assert np.array_equal(out["descL"], dL) and np.array_equal(out["descR"], dR)
+                assert out["n"] == o["n"] and np.array_equal(out["uright"], o["uright"]) and np.array_equal(out["depth"], o["depth"])
+        fe.close()
+
+
 def test_stereo_frontend_submit_wait_two_in_flight(ctx):
     """bench.py's double buffering: two front ends, the next batch submitted before the previous is waited for"""
     import ctypes as C

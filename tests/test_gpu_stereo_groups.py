@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, NF, SEED = 640, 480, 1000, 5
-CHUNK = 256  # ST_CHUNK of kernels_match.hip
+CHUNK = 256  # ST_CHUNK of kernels_stereo.hip
 
 
 class _Rig:
@@ -34,7 +34,7 @@ class _Rig:
         self.exR.close()
         self.ctx.close()
 
-    def check(self, kL, kR, dL, dR, expect_n=None):
+    def check(self, kL, kR, dL, dR, expect_n=None, expect_cut_n=None):
         """both median-cut settings against the oracle; -> the oracle's result without the cut"""
         fr = self.fr
         mbf, mb = fr["intr"]["mbf"], fr["intr"]["mb"]
@@ -45,6 +45,8 @@ class _Rig:
             print(f"nL {len(kL)} nR {len(kR)} cut {cut}: oracle n {o['n']} gpu n {g['n']}")
             if not cut and expect_n is not None:
                 assert o["n"] == expect_n
+            if cut and expect_cut_n is not None:
+                assert o["n"] == expect_cut_n
             assert g["n"] == o["n"]
             assert np.array_equal(g["uright"], o["uright"])
             assert np.array_equal(g["depth"], o["depth"])
@@ -117,6 +119,20 @@ def test_bucket_against_chunk_size(rig, nR, n):
     kL["y"] = np.float32(100.25)
     o = rig.check(kL, kR, fr["dL"], fr["dR"][:nR], expect_n=n)
     assert o["n"] > 0
+
+
+REG_CAP = 64 * 40  # 64 * SM_PER_LANE of kernels_stereo.hip: the most left keypoints whose SADs k_stereo_median holds in registers
+
+
+@pytest.mark.parametrize("nL,n,n_cut", [(REG_CAP, 582, 463), (REG_CAP + 1, 582, 463), (3024, 669, 540)])
+def test_median_cut_in_registers_and_looped(rig, nL, n, n_cut):
+    """k_stereo_median at and above its register capacity: the frame's left keypoints three times over, cut to the last count of
+    the register path, the first of the path that re-reads the SADs in every bisection step, and all of them; the cut acts
+    (the oracle drops a fifth of the matches)"""
+    fr = rig.fr
+    kL, dL = np.tile(fr["kL"], 3)[:nL], np.tile(fr["dL"], (3, 1))[:nL]
+    assert len(kL) == nL and len(dL) == nL
+    rig.check(kL, fr["kR"], dL, fr["dR"], expect_n=n, expect_cut_n=n_cut)
 
 
 def test_idempotent_when_enqueued_twice():

@@ -38,8 +38,8 @@ KERNELS = [
     ("kernels_pyramid.hip", "13k_pyr_cascadeE", "k_pyr_cascade"),
     ("kernels_fast.hip", "9k_compactE", "k_compact"),
     ("kernels_octree.hip", "8k_octreeE", "k_octree"),
-    ("kernels_match.hip", "14k_stereo_matchE", "k_stereo_match"),
-    ("kernels_frame.hip", "19k_fisheye_2nn_batchE", "k_fisheye_2nn_batch"),
+    ("kernels_stereo.hip", "14k_stereo_matchE", "k_stereo_match"),
+    ("kernels_fisheye.hip", "19k_fisheye_2nn_batchE", "k_fisheye_2nn_batch"),
     ("kernels_resolve.hip", "15k_resolve_batchILb0ELb1EE", "k_resolve_batch<false>"),
     ("kernels_resolve.hip", "15k_resolve_batchILb1ELb1EE", "k_resolve_batch<true>"),
     ("kernels_search_rows.hip", "19k_search_last_firstE", "k_search_last_first"),
