@@ -81,6 +81,11 @@ class BowKeyFrame(C.Structure):
     _fields_ = [("side", BowSide), ("has_point", C.c_void_p), ("n_left", C.c_int), ("n_un", C.c_int)]
 
 
+class BowCandidate(C.Structure):
+    """ft_bow_candidate: what ORBmatcher::SearchByBoW(KeyFrame, Frame) reads of a candidate KeyFrame"""
+    _fields_ = [("side", BowSide), ("has_point", C.c_void_p)]
+
+
 class TriangKeyFrame(C.Structure):
     """ft_triang_keyframe: what ORBmatcher::SearchForTriangulation reads of a KeyFrame"""
     _fields_ = [("n", C.c_int), ("n_left", C.c_int), ("keys", C.c_void_p), ("descriptors", C.c_void_p), ("n_nodes", C.c_int),
@@ -278,6 +283,7 @@ def lib() -> C.CDLL:
     L.ft_bow_transform.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, i, ip, vp, vp, vp, i, ip]
     L.ft_search_by_bow.argtypes = [vp, C.POINTER(BowSide), vp, C.POINTER(BowSide), i, f, i, vp, ip]
     L.ft_search_by_bow_keyframes.argtypes = [vp, C.POINTER(BowKeyFrame), i, C.POINTER(BowKeyFrame), f, i, vp, vp]
+    L.ft_search_by_bow_candidates.argtypes = [vp, C.POINTER(BowSide), i, i, i, C.POINTER(BowCandidate), f, i, vp, vp]
     L.ft_search_for_triangulation.argtypes = [vp, C.POINTER(TriangKeyFrame), i, C.POINTER(TriangKeyFrame), C.POINTER(TriangPair), i, i, i, vp, vp, vp]
     L.ft_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseTarget), vp, vp, vp, vp]
     L.ft_search_keyframe_sim3.argtypes = [vp, C.POINTER(FrameView), i, C.POINTER(Sim3Job)]

@@ -378,6 +378,32 @@ struct FtBowKfCall {
 int ft_launch_bow_kf_match(hipStream_t st, const FtBowKfCall &T);
 int ft_launch_bow_kf_finish(hipStream_t st, const FtBowKfCall &T);
 
+// ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (src/ORBmatcher.cc:322-524; kernels_bow_cand.hip) for one frame against every
+// candidate keyframe of a call (Tracking::Relocalization, src/Tracking.cc:3839-3860).  One arena as above; the frame's descriptors
+// alone are a pointer, because they may be read where a front end left them.
+struct FtBowCandSide {
+    int n, nNodes;                   // features, FeatureVector entries
+    unsigned nodes, offsets, feats;  // the FeatureVector in CSR form
+    unsigned desc, hasPoint, angles; // n x 32, uint8[n], float[n] (angles only with checkOrientation; the frame has no hasPoint)
+};
+struct FtBowCandJob {  // one candidate keyframe
+    FtBowCandSide K;
+    unsigned matches;  // int[F.n], -1 from the host's fill: the job's row, which also carries its claims
+};
+struct FtBowCandCall {
+    uint8_t *arena;
+    const uint8_t *frameDesc;  // F.n x 32: arena + F.desc, or the caller's device pointer
+    FtBowCandSide F;
+    unsigned jobs;      // FtBowCandJob[nCandidates]
+    unsigned nMatches;  // int[nCandidates]
+    int nCandidates, maxNodes;  // maxNodes: the largest K.nNodes of the call (the grid's x extent in waves)
+    int nLeft, checkOrientation;
+    float nnRatio;
+};
+// the two launches of a call, in this order
+int ft_launch_bow_cand_match(hipStream_t st, const FtBowCandCall &T);
+int ft_launch_bow_cand_finish(hipStream_t st, const FtBowCandCall &T);
+
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403; kernels_distinct.hip) for every map point of a call.  One arena
 // as above.  The host bins the points with a non-empty list by list length into four job lists, one behind the other in `jobs`:
 // N <= 8, N <= 16 (both served by k_distinct_short), N <= 64 (k_distinct_wave), N <= FT_DISTINCT_MAX_OBSERVATIONS

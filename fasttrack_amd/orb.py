@@ -1205,6 +1205,43 @@ def search_by_bow_keyframes(ctx: Context, kf1: BowKeyFrame, neighbours, nn_ratio
     return dict(matches12=mflat[:nn * n1].reshape(nn, n1), n=cnt[:nn])
 
 
+class BowCandidate:
+    """What ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) reads of a candidate KeyFrame (ft_bow_candidate).  side: BowSide
+    (mFeatVec, mDescriptors, the keypoint angles, the right camera's behind the left one's); has_point[i] = GetMapPoint(i) exists
+    and is not bad.  Owns the arrays."""
+
+    def __init__(self, side: BowSide, has_point):
+        self.side = side
+        self.has_point = np.ascontiguousarray(has_point, np.uint8)
+        assert len(self.has_point) == side.c.n
+        c = _capi.BowCandidate()
+        c.side = side.c
+        c.has_point = ptr(self.has_point)
+        self.c = c
+
+
+def search_by_bow_candidates(ctx: Context, frame: BowSide, candidates, frame_nleft=-1, nn_ratio=0.75, check_orientation=True,
+                             frame_device_ptr=None):
+    """ORBmatcher(nn_ratio, check_orientation).SearchByBoW(pKF, F, vpMapPointMatches) for the frame against every keyframe of
+    `candidates` (BowCandidate list) in one call (ft_search_by_bow_candidates; the loop of Tracking::Relocalization).
+    frame_device_ptr: DeviceBuffer or device address of the frame's descriptors (frame.n x 32 bytes, complete before the call), read in place
+    instead of frame.descriptors ->
+    dict(matches [N, frame.n] = feature index of candidate k whose map point vvpMapPointMatches[k][i] receives, or -1; n [N])"""
+    nk, nf = len(candidates), frame.c.n
+    K = (_capi.BowCandidate * max(nk, 1))(*[k.c for k in candidates])
+    F = frame.c
+    if frame_device_ptr is not None:
+        F = _capi.BowSide()
+        C.pointer(F)[0] = frame.c
+        dp = frame_device_ptr.ptr if isinstance(frame_device_ptr, DeviceBuffer) else frame_device_ptr
+        F.descriptors = dp.value if isinstance(dp, C.c_void_p) else int(dp)
+    cnt = np.zeros(max(nk, 1), np.int32)
+    mflat = np.full(max(nk * nf, 1), -1, np.int32)
+    check(lib().ft_search_by_bow_candidates(ctx._h, C.byref(F), int(frame_nleft), int(frame_device_ptr is not None), nk, K, float(nn_ratio),
+                                            int(bool(check_orientation)), ptr(mflat), ptr(cnt)))
+    return dict(matches=mflat[:nk * nf].reshape(nk, nf), n=cnt[:nk])
+
+
 class TriangKeyFrame:
     """What ORBmatcher::SearchForTriangulation reads of a KeyFrame (ft_triang_keyframe).  keys: KP_DTYPE records (mvKeysUn, or
     mvKeys followed by mvKeysRight when n_left != -1); fv_*: mFeatVec as Vocabulary.transform returns it; has_point[i] =

@@ -715,6 +715,36 @@ typedef struct ft_bow_side {
 } ft_bow_side;
 FT_API int ft_search_by_bow(ft_context *ctx, const ft_bow_side *kf, const uint8_t *kf_has_point, const ft_bow_side *frame,
                             int frame_nleft, float nn_ratio, int check_orientation, int *matches, int *n_matches);
+/* The same search for one frame against ALL the candidate keyframes of a call: the loop of Tracking::Relocalization
+ * (src/Tracking.cc:3839-3860; the candidates' isBad() test stays with the caller), whose calls share the frame and are
+ * independent of each other.  matches[k * frame->n + i] = the feature index of keyframe k whose map point
+ * vvpMapPointMatches[k][i] receives, or -1; n_matches[k] = the return value of the reference's call for candidate k.  Row k is bit
+ * for bit what ft_search_by_bow(ctx, &keyframes[k].side, keyframes[k].has_point, frame, frame_nleft, ...) delivers: <= TH_LOW
+ * (50 is accepted), the ratio as one fp32 product with a strict <, the first of the node's list at the smallest distance, the
+ * frame features an earlier keyframe feature of the node has claimed skipped, the right camera's second best pair with its ratio
+ * test disabled (:458), then the rotation histogram of kf angle - frame angle, ComputeThreeMaxima and the removal.  A claim of one
+ * candidate is never visible to another.
+ * frame_descriptors_on_device != 0: frame->descriptors is a device pointer (ft_stereo_frontend_device_descriptors,
+ * ft_device_malloc memory, ...); the descriptors are read in place and never copied.  They must be complete before the call:
+ * written by work on the context's own stream, or by work the caller has waited for (as for ft_bow_transform's on_device).
+ * Launches per call: 2 whatever n_keyframes (the walk of every (candidate, node) unit; histogram, removal and counts, a workgroup
+ * per candidate), one copy up, one copy down, one wait; kernel timing names them kernel.bow_cand_match / kernel.bow_cand_finish.
+ * Stats: search_by_bow_candidates.total (ms), .launches, and .up_bytes (the bytes of the copy up, summed in the stat's value).
+ * frame->n == 0 or n_keyframes == 0 returns without a launch, n_matches all 0.  A candidate with n == 0, without nodes, without map
+ * points or without a shared node gives a row of -1 and 0.
+ * FT_ERR_INVALID: what ft_search_by_bow rejects in a side, on any side; frame_nleft outside [-1, frame->n]; null has_point with
+ * n > 0; check_orientation without angles on a non-empty side; a frame feature listed twice in the frame's FeatureVector (the
+ * independence of the nodes rests on a frame feature sitting in one node); n_keyframes outside [0, 65535]; null matches /
+ * n_matches when there is something to write.  FT_ERR_CAPACITY when one call's block exceeds 4 GB.  Nothing is written on an error. */
+typedef struct ft_bow_candidate {
+    ft_bow_side side;          /* KeyFrame::N, mFeatVec as CSR, mDescriptors, angles[n] (right camera behind the left one, as for ft_search_by_bow) */
+    const uint8_t *has_point;  /* [side.n]  GetMapPoint(i) != NULL && !isBad()  (src/ORBmatcher.cc:354-360) */
+} ft_bow_candidate;
+FT_API int ft_search_by_bow_candidates(ft_context *ctx, const ft_bow_side *frame, int frame_nleft,
+                                       int frame_descriptors_on_device,
+                                       int n_keyframes, const ft_bow_candidate *keyframes /* [n_keyframes] */,
+                                       float nn_ratio, int check_orientation,
+                                       int *matches /* n_keyframes x frame->n */, int *n_matches /* [n_keyframes] */);
 
 /* ----------------------------------------------------------------------------------------------
  * ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint*> &vpMatches12) (src/ORBmatcher.cc:864-1004),

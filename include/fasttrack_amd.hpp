@@ -617,6 +617,44 @@ inline std::vector<int> SearchByBoW(Context &ctx, const BowKeyFrame &kf1, const 
     return nmatches;
 }
 
+// What ORBmatcher::SearchByBoW(KeyFrame *pKF, Frame &F, vpMapPointMatches) reads of a candidate KeyFrame: mFeatVec, mDescriptors
+// (N rows), hasPoint[i] = GetMapPoint(i) && !GetMapPoint(i)->isBad(), angles = cv::KeyPoint::angle per feature (the right
+// camera's after the left one's).
+struct BowCandidate {
+    const ORBVocabulary::FeatureVector *mFeatVec = nullptr;
+    const uint8_t *mDescriptors = nullptr;
+    int N = 0;
+    const uint8_t *hasPoint = nullptr;
+    const float *angles = nullptr;
+};
+// ORBmatcher(nnRatio, checkOrientation).SearchByBoW(vpCandidateKFs[k], F, vvpMapPointMatches[k]) for the frame against every
+// candidate in one call (ft_search_by_bow_candidates; the loop of Tracking::Relocalization, src/Tracking.cc:3839-3860, whose
+// isBad() test on the candidates stays with the caller).  fDescriptorsOnDevice: fDescriptors is a device pointer, read in place.
+// vvMatches[k][i] = index into candidates[k]'s GetMapPointMatches() or -1:
+// `vvpMapPointMatches[k][i] = m < 0 ? nullptr : vpMapPointsKF[m]`.  Returns nmatches per candidate.
+inline std::vector<int> SearchByBoW(Context &ctx, const std::vector<BowCandidate> &candidates, const ORBVocabulary::FeatureVector &fFeatVec,
+                                    const uint8_t *fDescriptors, int fN, const float *fAngles, int fNleft, bool fDescriptorsOnDevice,
+                                    float nnRatio, bool checkOrientation, std::vector<std::vector<int>> &vvMatches) {
+    const size_t nk = candidates.size(), nf = fN > 0 ? (size_t)fN : 0;
+    std::vector<detail::BowCsr> csr(nk + 1);
+    csr[nk] = detail::flattenFeatVec(fFeatVec);
+    const ft_bow_side F = detail::bowSide(csr[nk], fN, fDescriptors, fAngles);
+    std::vector<ft_bow_candidate> K(nk);
+    for (size_t k = 0; k < nk; k++) {
+        if (!candidates[k].mFeatVec) throw std::invalid_argument("SearchByBoW: a candidate without mFeatVec");
+        csr[k] = detail::flattenFeatVec(*candidates[k].mFeatVec);
+        K[k].side = detail::bowSide(csr[k], candidates[k].N, candidates[k].mDescriptors, candidates[k].angles);
+        K[k].has_point = candidates[k].hasPoint;
+    }
+    std::vector<int> flat(nk * nf + 1, -1), nmatches(nk + 1, 0);
+    check(ft_search_by_bow_candidates(ctx.handle(), &F, fNleft, fDescriptorsOnDevice ? 1 : 0, (int)nk, K.data(), nnRatio,
+                                      checkOrientation ? 1 : 0, flat.data(), nmatches.data()));
+    vvMatches.assign(nk, {});
+    for (size_t k = 0; k < nk; k++) vvMatches[k].assign(flat.begin() + k * nf, flat.begin() + (k + 1) * nf);
+    nmatches.resize(nk);
+    return nmatches;
+}
+
 // ORBmatcher(0.6, mbCheckOrientation).SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse)
 // (src/ORBmatcher.cc:1006-1245) for pKF1 against every neighbour of LocalMapping::CreateNewMapPoints in one call
 // (ft_search_for_triangulation): vpKF2 are the neighbours that passed the caller's baseline filter, vPairs the constants of each
