@@ -99,6 +99,13 @@ class TriangPair(C.Structure):
     _fields_ = [("ep", C.c_float * 2), ("F12", C.c_float * 9), ("R12", C.c_float * 36), ("t12", C.c_float * 12), ("kb8_precision", C.c_float)]
 
 
+class NewPointGeometry(C.Structure):
+    """ft_newpoint_geometry: what the triangulation of LocalMapping::CreateNewMapPoints reads of a KeyFrame besides ft_triang_keyframe"""
+    _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("Tcw_right", C.c_float * 12), ("Ow_right", C.c_float * 3),
+                ("Rwc", C.c_float * 9), ("twc", C.c_float * 3)] + [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")] + [
+                    ("depth", C.c_void_p), ("keys_raw", C.c_void_p), ("kb8_precision", C.c_float)]
+
+
 class FusePoints(C.Structure):
     """ft_fuse_points: the map points of a Fuse call"""
     _fields_ = [("M", C.c_int), ("world_pos", C.c_void_p), ("normal", C.c_void_p), ("max_distance", C.c_void_p),
@@ -285,6 +292,10 @@ def lib() -> C.CDLL:
     L.ft_search_by_bow_keyframes.argtypes = [vp, C.POINTER(BowKeyFrame), i, C.POINTER(BowKeyFrame), f, i, vp, vp]
     L.ft_search_by_bow_candidates.argtypes = [vp, C.POINTER(BowSide), i, i, i, C.POINTER(BowCandidate), f, i, vp, vp]
     L.ft_search_for_triangulation.argtypes = [vp, C.POINTER(TriangKeyFrame), i, C.POINTER(TriangKeyFrame), C.POINTER(TriangPair), i, i, i, vp, vp, vp]
+    NG = C.POINTER(NewPointGeometry)
+    L.ft_triangulate_new_points.argtypes = [vp, C.POINTER(TriangKeyFrame), NG, i, C.POINTER(TriangKeyFrame), NG, vp, i, i, f, f, vp, vp, vp, vp]
+    L.ft_search_and_triangulate.argtypes = [vp, C.POINTER(TriangKeyFrame), NG, i, C.POINTER(TriangKeyFrame), NG, C.POINTER(TriangPair), i, i, i,
+                                            i, i, f, f, vp, vp, vp, vp, vp, vp, vp]
     L.ft_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseTarget), vp, vp, vp, vp]
     L.ft_search_keyframe_sim3.argtypes = [vp, C.POINTER(FrameView), i, C.POINTER(Sim3Job)]
     L.ft_distinctive_descriptors.argtypes = [vp, i, vp, vp, vp, vp, vp]

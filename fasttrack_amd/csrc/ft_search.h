@@ -354,6 +354,29 @@ struct FtTriangCall {
 int ft_launch_triang_match(hipStream_t st, const FtTriangCall &T);
 int ft_launch_triang_finish(hipStream_t st, const FtTriangCall &T);
 
+// The per-match text of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:483-692; kernels_newpoints.hip) on the match rows of
+// the call above, in the same arena: what ft_newpoint_geometry adds to a keyframe, per neighbour the rows it writes.
+struct FtNewPointSide {
+    float Tcw[2][12], Ow[2][3];  // GetPose() / GetRightPose() as matrix3x4() row-major, GetCameraCenter() / GetRightCameraCenter()
+    float Rwc[9], twc[3];        // mRwc, mTwc.translation() (KeyFrame::UnprojectStereo)
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf, precision;
+    unsigned depth, keysRaw;     // float[n] mvDepth, ft_keypoint[n] mvKeys; FT_TRIANG_NONE: no stereo keypoint / the keys of the side
+};
+struct FtNewPointJob {  // one neighbour
+    FtNewPointSide G2;
+    unsigned status, x3d;  // int[K1.n], float[3 * K1.n]
+};
+struct FtNewPointCall {
+    unsigned g1;              // FtNewPointSide of keyframe 1
+    unsigned jobs;            // FtNewPointJob[nNeighbours]
+    unsigned nPoints;         // int[nNeighbours], staged as 0: the workgroups of a neighbour add to it
+    unsigned firstNeighbour;  // unsigned[K1.n], staged as 0xffffffff (-1): atomic minimum over the accepting neighbours
+    int inertial, farPoints;
+    float thFar, ratioFactor;
+};
+// one launch, behind ft_launch_triang_finish or on staged match rows: reads FtTriangJob::matches, FtTriangSide keys / uright / sf / sigma2 / cam
+int ft_launch_triang_points(hipStream_t st, const FtTriangCall &T, const FtNewPointCall &P);
+
 // ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:864-1004; kernels_bow_kf.hip) for keyframe 1 against every
 // neighbour of a call.  One arena as above: records hold byte offsets into it.
 struct FtBowKfSide {

@@ -1,5 +1,5 @@
 // Host side of the projection searches, shared by the translation units of the entry-point families (search_view.cpp,
-// tracked_frame.cpp, init_search.cpp, reloc_search.cpp, triang_search.cpp, fuse_search.cpp, sim3_search.cpp, tracked_batch.cpp; bow.cpp, bow_kf_search.cpp,
+// tracked_frame.cpp, init_search.cpp, reloc_search.cpp, triang_search.cpp and newpoints.cpp (through triang_host.h), fuse_search.cpp, sim3_search.cpp, tracked_batch.cpp; bow.cpp, bow_kf_search.cpp,
 // distinct_desc.cpp and fisheye_match.cpp for the call skeleton at the end: Arena, CallScope): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
 // (reference include/Kernels/KernelController.h:40-46) together with the acceptance loops the reference keeps in the caller
 // (src/ORBmatcher.cc:241-308, 2013-2081).  Windowing, level/box tests and every Hamming distance run on the device

@@ -1315,6 +1315,84 @@ def search_for_triangulation(ctx: Context, kf1: TriangKeyFrame, neighbours, pair
     return dict(matches12=m, n=cnt[:nn], best_dist=bd, pairs=out)
 
 
+class NewPointGeometry:
+    """What the triangulation of LocalMapping::CreateNewMapPoints reads of a KeyFrame besides TriangKeyFrame (ft_newpoint_geometry).
+    Tcw / Tcw_right: GetPose() / GetRightPose() as 3 x 4 (or 4 x 4) matrices, Ow / Ow_right the camera centres; Rwc, twc: mRwc and
+    mTwc.translation() (None: Rcw^T and Ow); intr: fx fy cx cy (invfx = 1.0f / fx as KeyFrame holds it, or given); depth: mvDepth
+    or None; keys_raw: mvKeys (KP_DTYPE) or None = the keyframe's keys.  Owns the arrays."""
+
+    def __init__(self, Tcw, Ow, intr, mb=0.0, mbf=0.0, Tcw_right=None, Ow_right=None, Rwc=None, twc=None, depth=None, keys_raw=None,
+                 invfx=None, invfy=None, kb8_precision=1e-6):
+        f32 = np.float32
+        T = np.asarray(Tcw, f32).reshape(-1, 4)[:3]
+        Tr = T if Tcw_right is None else np.asarray(Tcw_right, f32).reshape(-1, 4)[:3]
+        Ow = np.asarray(Ow, f32).reshape(3)
+        Owr = Ow if Ow_right is None else np.asarray(Ow_right, f32).reshape(3)
+        Rwc = np.ascontiguousarray(T[:, :3].T) if Rwc is None else np.asarray(Rwc, f32).reshape(3, 3)
+        twc = Ow if twc is None else np.asarray(twc, f32).reshape(3)
+        self.depth = None if depth is None else np.ascontiguousarray(depth, f32)
+        self.keys_raw = None if keys_raw is None else np.ascontiguousarray(keys_raw, _capi.KP_DTYPE)
+        g = _capi.NewPointGeometry()
+        g.Tcw[:], g.Tcw_right[:] = [float(v) for v in T.reshape(-1)], [float(v) for v in Tr.reshape(-1)]
+        g.Ow[:], g.Ow_right[:] = [float(v) for v in Ow], [float(v) for v in Owr]
+        g.Rwc[:], g.twc[:] = [float(v) for v in Rwc.reshape(-1)], [float(v) for v in twc]
+        fx, fy, cx, cy = [f32(v) for v in list(intr)[:4]]
+        g.fx, g.fy, g.cx, g.cy = float(fx), float(fy), float(cx), float(cy)
+        g.invfx = float(f32(1.0) / fx if invfx is None else f32(invfx))
+        g.invfy = float(f32(1.0) / fy if invfy is None else f32(invfy))
+        g.mb, g.mbf, g.kb8_precision = float(f32(mb)), float(f32(mbf)), float(f32(kb8_precision))
+        g.depth = None if self.depth is None else ptr(self.depth)
+        g.keys_raw = None if self.keys_raw is None else ptr(self.keys_raw)
+        self.c = g
+
+
+def _new_point_outputs(nn, n1):
+    return (np.zeros(max(nn * n1, 1), np.int32), np.zeros(max(nn * n1 * 3, 1), np.float32), np.zeros(max(nn, 1), np.int32),
+            np.full(max(n1, 1), -1, np.int32))
+
+
+def _new_point_result(nn, n1, st, x3, npts, first):
+    return dict(status=st[:nn * n1].reshape(nn, n1), x3d=x3[:nn * n1 * 3].reshape(nn, n1, 3), n_points=npts[:nn], first_neighbour=first[:n1])
+
+
+def triangulate_new_points(ctx: Context, kf1: TriangKeyFrame, g1: NewPointGeometry, neighbours, geometries, matches12, inertial=False,
+                           far_points=False, th_far_points=0.0, ratio_factor=1.8):
+    """The per-match text of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:483-692) on host match rows
+    (ft_triangulate_new_points).  matches12 [k, kf1.n] as search_for_triangulation returns it; ratio_factor = 1.5f * mfScaleFactor
+    -> dict(status [k, n1], x3d [k, n1, 3], n_points [k], first_neighbour [n1])"""
+    nn, n1 = len(neighbours), kf1.c.n
+    assert len(geometries) == nn
+    K2 = (_capi.TriangKeyFrame * max(nn, 1))(*[k.c for k in neighbours])
+    G2 = (_capi.NewPointGeometry * max(nn, 1))(*[g.c for g in geometries])
+    m = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+    assert m.size == nn * n1
+    st, x3, npts, first = _new_point_outputs(nn, n1)
+    check(lib().ft_triangulate_new_points(ctx._h, C.byref(kf1.c), C.byref(g1.c), nn, K2, G2, ptr(m) if m.size else None, int(bool(inertial)),
+                                          int(bool(far_points)), float(th_far_points), float(ratio_factor), ptr(st), ptr(x3), ptr(npts),
+                                          ptr(first)))
+    return _new_point_result(nn, n1, st, x3, npts, first)
+
+
+def search_and_triangulate(ctx: Context, kf1: TriangKeyFrame, g1: NewPointGeometry, neighbours, geometries, pairs, only_stereo=False,
+                           coarse=False, check_orientation=True, inertial=False, far_points=False, th_far_points=0.0, ratio_factor=1.8):
+    """search_for_triangulation followed by triangulate_new_points in one call (ft_search_and_triangulate): the match rows stay on
+    the device in between -> the keys of both results"""
+    nn, n1 = len(neighbours), kf1.c.n
+    assert len(pairs) == nn and len(geometries) == nn
+    K2 = (_capi.TriangKeyFrame * max(nn, 1))(*[k.c for k in neighbours])
+    G2 = (_capi.NewPointGeometry * max(nn, 1))(*[g.c for g in geometries])
+    P = (_capi.TriangPair * max(nn, 1))(*pairs)
+    cnt = np.zeros(max(nn, 1), np.int32)
+    mflat, bflat = np.full(max(nn * n1, 1), -1, np.int32), np.full(max(nn * n1, 1), 50, np.int32)
+    st, x3, npts, first = _new_point_outputs(nn, n1)
+    check(lib().ft_search_and_triangulate(ctx._h, C.byref(kf1.c), C.byref(g1.c), nn, K2, G2, P, int(bool(only_stereo)), int(bool(coarse)),
+                                          int(bool(check_orientation)), int(bool(inertial)), int(bool(far_points)), float(th_far_points),
+                                          float(ratio_factor), ptr(mflat), ptr(cnt), ptr(bflat), ptr(st), ptr(x3), ptr(npts), ptr(first)))
+    out = _new_point_result(nn, n1, st, x3, npts, first)
+    out.update(matches12=mflat[:nn * n1].reshape(nn, n1), n=cnt[:nn], best_dist=bflat[:nn * n1].reshape(nn, n1))
+    return out
+
+
 def inv_level_sigma2(scale_factors):
     """mvInvLevelSigma2 as ORBextractor builds it: 1.0f / (mvScaleFactor[i] * mvScaleFactor[i])"""
     sf = np.asarray(scale_factors, np.float32)

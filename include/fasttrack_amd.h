@@ -842,6 +842,78 @@ FT_API int ft_search_for_triangulation(ft_context *ctx, const ft_triang_keyframe
                                        int only_stereo, int coarse, int check_orientation, int *matches12 /* n_neighbours x kf1->n */,
                                        int *n_matches /* [n_neighbours] */, int *best_dist /* may be NULL */);
 
+/* ----------------------------------------------------------------------------------------------
+ * The triangulation of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:483-692): what the reference does with every pair
+ * of vMatchedPairs behind SearchForTriangulation, here for every match of keyframe 1 against ALL its neighbours in one launch,
+ * either on host match rows (ft_triangulate_new_points) or on the rows the matcher left on the device
+ * (ft_search_and_triangulate: the matches neither come down nor go up in between).
+ * Per match (idx1, idx2) of neighbour k, operation for operation, float without contraction:
+ *   keypoints, bRight, bStereo as in ft_search_for_triangulation (bStereo = !two_cameras && uright[idx] >= 0, :492, :501); two-camera
+ *   keyframes take pose, camera centre and camera of the pairing ll / lr / rl / rr per match (:505-555).
+ *   xn = pCamera->unprojectEig(kp.pt) (Pinhole.cpp:61-64 with cam[]; KannalaBrandt8.cpp:111-143 with kb8_precision), ray = Rwc *
+ *   xn with Rwc = Rcw.transpose() (a three-term sum is e0 + (e1 + e2)), cosParallaxRays = ray1.dot(ray2) / (ray1.norm() *
+ *   ray2.norm()) (:558-563).  cosParallaxStereo1 = cosf(2 * atan2f(mb1 / 2, depth1[idx1])) when bStereo1, ELSE IF bStereo2
+ *   cosParallaxStereo2 likewise, each cosParallaxRays + 1 otherwise; cosParallaxStereo = std::min of the two (:565-576).  The
+ *   float overloads bind: LocalMapping.cc sees `using namespace std` through LocalMapping.h -> KeyFrame.h -> ORBVocabulary.h ->
+ *   DBoW2/TemplatedVocabulary.h:36.
+ *   The branch (:582-604): cosParallaxRays < cosParallaxStereo && > 0 && (bStereo1 || bStereo2 || (double) < 0.9996 (inertial) /
+ *   0.9998 (not inertial)): GeometricTools::Triangulate (src/GeometricTools.cc:47-66; rows xn(0) * T.row(2) - T.row(0), ... in
+ *   float, false when the fourth component of the null vector == 0, else head(3) / w); else bStereo1 && cosParallaxStereo1 <
+ *   cosParallaxStereo2: KeyFrame::UnprojectStereo of keyframe 1 (src/KeyFrame.cc:755-772: keys_raw, x = (u - cx) * z * invfx,
+ *   x3D = Rwc * x3Dc + twc, false when depth <= 0); else the same for keyframe 2; else the pair is dropped.
+ *   z = Rcw.row(2).dot(x3D) + tcw(2) > 0 in both keyframes; the reprojection tests (:621-672): non-stereo pCamera->project(x, y, z)
+ *   against kp.pt with (double)(ex^2 + ey^2) > 5.991 * sigma2, stereo u = fx * x * invz + cx (invz = (float)(1.0 / z)), u_r = u -
+ *   mbf * invz with > 7.8 * sigma2 - keyframe 2's u_r with KEYFRAME 1's mbf, as the reference's :665 has it; scale consistency
+ *   (:675-691): dist = (x3D - Ow).norm(), zero distances, far_points && (dist >= th_far_points), ratioDist = dist2 / dist1 against
+ *   scale_factors1[kp1.octave] / scale_factors2[kp2.octave] and ratio_factor (1.5f * mfScaleFactor).  A NaN passes or fails where the
+ *   C++ comparisons let it.
+ * Outputs, in the shape of matches12: status[k * kf1->n + idx1] =
+ *    0 no match            1 accepted, triangulated     2 accepted, stereo point of keyframe 1     3 ... of keyframe 2
+ *   -1 low parallax and no stereo (:603)   -2 Triangulate / UnprojectStereo returned false   -3 z1 <= 0   -4 z2 <= 0
+ *   -5 / -6 reprojection error in keyframe 1 / 2     -7 zero distance     -8 far point     -9 scale inconsistency
+ * x3d[3 * (k * kf1->n + idx1)]: the point where status > 0, zeros elsewhere; n_points[k]: the accepted points of neighbour k;
+ * first_neighbour[idx1]: the smallest k with status > 0, -1 = none.
+ * LOOP ORDER.  The reference attaches the new point to idx1 at the first neighbour that accepts it, and its matcher then skips
+ * idx1 for the later neighbours (pMP1, src/ORBmatcher.cc:1073).  The batched calls treat the neighbours independently: a later
+ * neighbour may report a match and a point for an idx1 that an earlier one took.  first_neighbour[idx1] says which neighbour
+ * wins: the caller attaches only the point of that neighbour.  This is not the reference's loop in one respect: there the
+ * features taken by earlier neighbours are missing from a later neighbour's rotation histogram (:1186-1232), here they are in
+ * it, so with check_orientation the three kept bins of a later neighbour can differ.  n_neighbours == 1 with has_point updated
+ * between the calls is the reference's loop exactly.
+ * NOT pinned bit for bit: the null vector is a one-sided Jacobi SVD in double, narrowed to float, where the reference runs Eigen's
+ * float JacobiSVD (as documented at ft_fisheye_stereo); x3d of triangulated points, and the status of pairs that sit on a
+ * threshold, agree with the reference to its rounding error.  Stereo points (status 2, 3) and everything in front of the SVD are
+ * the reference's floats.
+ * ft_triangulate_new_points: one copy up, ONE launch (kernel.triang_points: a workgroup per neighbour and 256 slots of its row,
+ * the slots that hold a match compacted in front of the arithmetic), one copy down, one wait; the fv_*, descriptors and has_point
+ * fields of the keyframes are not read and may be NULL.  ft_search_and_triangulate: the arguments and results of
+ * ft_search_for_triangulation plus the above in one arena: one copy up, 3 launches, one copy down, one wait, whatever
+ * n_neighbours.  kf1->n == 0 or n_neighbours == 0 returns without a launch (counts 0).
+ * FT_ERR_INVALID: what ft_search_for_triangulation rejects of the fields that are read; a matches12 entry >= kf2[k].n; a keypoint
+ * with uright >= 0 in a keyframe with one camera and depth == NULL; keyframes that differ in two_cameras or cam_model.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ft_newpoint_geometry {   /* one per keyframe */
+    float Tcw[12], Ow[3];               /* GetPose().matrix3x4() row-major, GetCameraCenter() */
+    float Tcw_right[12], Ow_right[3];   /* GetRightPose(), GetRightCameraCenter(); read when two_cameras */
+    float Rwc[9], twc[3];               /* mRwc, mTwc.translation(): KeyFrame::UnprojectStereo (NOT Rcw^T: taken as given) */
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+    const float *depth;                 /* [n] mvDepth, NULL: no stereo keypoints */
+    const ft_keypoint *keys_raw;        /* [n] mvKeys for UnprojectStereo, NULL: same as keys */
+    float kb8_precision;                /* KannalaBrandt8::precision of the keyframe's cameras (unprojectEig); unread for pinhole */
+} ft_newpoint_geometry;
+FT_API int ft_triangulate_new_points(ft_context *ctx, const ft_triang_keyframe *kf1, const ft_newpoint_geometry *g1, int n_neighbours,
+                                     const ft_triang_keyframe *kf2 /* [n_neighbours] */, const ft_newpoint_geometry *g2 /* [n_neighbours] */,
+                                     const int *matches12 /* n_neighbours x kf1->n, -1 = no match */, int inertial, int far_points,
+                                     float th_far_points, float ratio_factor, int *status /* n_neighbours x kf1->n */,
+                                     float *x3d /* n_neighbours x kf1->n x 3 */, int *n_points /* [n_neighbours] */,
+                                     int *first_neighbour /* [kf1->n] */);
+FT_API int ft_search_and_triangulate(ft_context *ctx, const ft_triang_keyframe *kf1, const ft_newpoint_geometry *g1, int n_neighbours,
+                                     const ft_triang_keyframe *kf2 /* [n_neighbours] */, const ft_newpoint_geometry *g2 /* [n_neighbours] */,
+                                     const ft_triang_pair *pairs /* [n_neighbours] */, int only_stereo, int coarse, int check_orientation,
+                                     int inertial, int far_points, float th_far_points, float ratio_factor,
+                                     int *matches12 /* n_neighbours x kf1->n */, int *n_matches /* [n_neighbours] */,
+                                     int *best_dist /* may be NULL */, int *status, float *x3d, int *n_points, int *first_neighbour);
+
 /* ------------------------------------------------------------------------------------------------
  * ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, th, bRight) (src/ORBmatcher.cc:1247-1437) and
  * ORBmatcher::Fuse(KeyFrame *pKF, Sophus::Sim3f &Scw, vpPoints, th, vpReplacePoint) (:1439-1554): the searches

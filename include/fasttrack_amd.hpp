@@ -679,6 +679,71 @@ inline std::vector<int> SearchForTriangulation(Context &ctx, const ft_triang_key
     return nmatches;
 }
 
+// A point LocalMapping::CreateNewMapPoints would create (src/LocalMapping.cc:694): the pair, x3D and bPointStereo
+struct NewMapPoint {
+    size_t idx1, idx2;
+    float x3D[3];
+    bool bPointStereo;
+};
+namespace detail {
+inline std::vector<std::vector<NewMapPoint>> newMapPoints(size_t nn, size_t n1, const std::vector<int> &matches12, const std::vector<int> &status,
+                                                          const std::vector<float> &x3d) {
+    std::vector<std::vector<NewMapPoint>> out(nn);
+    for (size_t k = 0; k < nn; k++)
+        for (size_t i = 0; i < n1; i++) {
+            const size_t s = k * n1 + i;
+            if (status[s] <= 0) continue;
+            out[k].push_back(NewMapPoint{i, (size_t)matches12[s], {x3d[3 * s], x3d[3 * s + 1], x3d[3 * s + 2]}, status[s] != 1});
+        }
+    return out;
+}
+}  // namespace detail
+
+// The triangulation loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:483-692) on the vMatchedPairs of every neighbour
+// (ft_triangulate_new_points): mbInertial, mbFarPoints, mThFarPoints, ratioFactor = 1.5f * mfScaleFactor.  Returns per neighbour the
+// accepted points in ascending idx1; firstNeighbour[idx1] (if asked for) is the neighbour whose point the reference's loop attaches
+// to idx1, -1 = none (see the loop-order note in fasttrack_amd.h).
+inline std::vector<std::vector<NewMapPoint>> TriangulateNewPoints(Context &ctx, const ft_triang_keyframe &pKF1, const ft_newpoint_geometry &g1,
+                                                                  const std::vector<ft_triang_keyframe> &vpKF2,
+                                                                  const std::vector<ft_newpoint_geometry> &vg2,
+                                                                  const std::vector<std::vector<std::pair<size_t, size_t>>> &vMatchedPairs,
+                                                                  bool mbInertial, bool mbFarPoints, float mThFarPoints, float ratioFactor,
+                                                                  std::vector<int> *firstNeighbour = nullptr) {
+    const size_t nn = vpKF2.size(), n1 = pKF1.n > 0 ? (size_t)pKF1.n : 0;
+    if (vg2.size() != nn || vMatchedPairs.size() != nn) throw std::invalid_argument("TriangulateNewPoints: one geometry and one pair list per neighbour");
+    std::vector<int> matches12(nn * n1 + 1, -1), status(nn * n1 + 1, 0), nPoints(nn + 1, 0), first(n1 + 1, -1);
+    std::vector<float> x3d(3 * (nn * n1 + 1), 0.f);
+    for (size_t k = 0; k < nn; k++)
+        for (const auto &m : vMatchedPairs[k]) {
+            if (m.first >= n1) throw std::invalid_argument("TriangulateNewPoints: idx1 out of range");
+            matches12[k * n1 + m.first] = (int)m.second;
+        }
+    check(ft_triangulate_new_points(ctx.handle(), &pKF1, &g1, (int)nn, vpKF2.data(), vg2.data(), matches12.data(), mbInertial ? 1 : 0,
+                                    mbFarPoints ? 1 : 0, mThFarPoints, ratioFactor, status.data(), x3d.data(), nPoints.data(), first.data()));
+    if (firstNeighbour) firstNeighbour->assign(first.begin(), first.begin() + n1);
+    return detail::newMapPoints(nn, n1, matches12, status, x3d);
+}
+
+// SearchForTriangulation and the loop above in one call (ft_search_and_triangulate): the matches stay on the device in between.
+inline std::vector<std::vector<NewMapPoint>> SearchAndTriangulate(Context &ctx, const ft_triang_keyframe &pKF1, const ft_newpoint_geometry &g1,
+                                                                  const std::vector<ft_triang_keyframe> &vpKF2,
+                                                                  const std::vector<ft_newpoint_geometry> &vg2,
+                                                                  const std::vector<ft_triang_pair> &vPairs, bool bOnlyStereo, bool bCoarse,
+                                                                  bool mbCheckOrientation, bool mbInertial, bool mbFarPoints, float mThFarPoints,
+                                                                  float ratioFactor, std::vector<int> *firstNeighbour = nullptr,
+                                                                  std::vector<int> *nmatches = nullptr) {
+    const size_t nn = vpKF2.size(), n1 = pKF1.n > 0 ? (size_t)pKF1.n : 0;
+    if (vg2.size() != nn || vPairs.size() != nn) throw std::invalid_argument("SearchAndTriangulate: one geometry and one ft_triang_pair per neighbour");
+    std::vector<int> matches12(nn * n1 + 1, -1), status(nn * n1 + 1, 0), nPoints(nn + 1, 0), first(n1 + 1, -1), nm(nn + 1, 0);
+    std::vector<float> x3d(3 * (nn * n1 + 1), 0.f);
+    check(ft_search_and_triangulate(ctx.handle(), &pKF1, &g1, (int)nn, vpKF2.data(), vg2.data(), vPairs.data(), bOnlyStereo ? 1 : 0,
+                                    bCoarse ? 1 : 0, mbCheckOrientation ? 1 : 0, mbInertial ? 1 : 0, mbFarPoints ? 1 : 0, mThFarPoints, ratioFactor,
+                                    matches12.data(), nm.data(), nullptr, status.data(), x3d.data(), nPoints.data(), first.data()));
+    if (firstNeighbour) firstNeighbour->assign(first.begin(), first.begin() + n1);
+    if (nmatches) nmatches->assign(nm.begin(), nm.begin() + nn);
+    return detail::newMapPoints(nn, n1, matches12, status, x3d);
+}
+
 // ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) (src/ORBmatcher.cc:1247-1437) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)
 // (:1439-1554) for one list of map points against every target (keyframe, camera) of LocalMapping::SearchInNeighbors or
 // LoopClosing::SearchAndFuse in one call (ft_fuse_search).  vpMapPoints are the arrays of the points, vTargets one record per
