@@ -18,6 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "fasttrack_amd.h")
 
 FT_OK, FT_ERR_INVALID, FT_ERR_NO_DEVICE, FT_ERR_HIP, FT_ERR_CAPACITY, FT_ERR_EMPTY = 0, -1, -2, -3, -4, -5
 DISTINCT_MAX_OBSERVATIONS = 1024  # FT_DISTINCT_MAX_OBSERVATIONS: the longest list of ft_distinctive_descriptors
+POSE_OPT_MAX_EDGES = 2000  # FT_POSE_OPT_MAX_EDGES: the most correspondences of a frame of ft_pose_optimization
 KFDB_MAX_QUERY_WORDS = 4096  # FT_KFDB_MAX_QUERY_WORDS: the longest query of ft_kfdb_score
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
@@ -104,6 +105,18 @@ class NewPointGeometry(C.Structure):
     _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("Tcw_right", C.c_float * 12), ("Ow_right", C.c_float * 3),
                 ("Rwc", C.c_float * 9), ("twc", C.c_float * 3)] + [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")] + [
                     ("depth", C.c_void_p), ("keys_raw", C.c_void_p), ("kb8_precision", C.c_float)]
+
+
+class PoseOptFrame(C.Structure):
+    """ft_pose_opt_frame: what Optimizer::PoseOptimization reads of a Frame"""
+    _fields_ = [("N", C.c_int), ("Nleft", C.c_int), ("has_point", C.c_void_p), ("world_pos", C.c_void_p), ("keys", C.c_void_p),
+                ("keys_right", C.c_void_p), ("uright", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("nlevels", C.c_int),
+                ("cam_model", C.c_int), ("cam", C.c_float * 8), ("cam2", C.c_float * 8), ("mbf", C.c_float), ("Tcw", SE3), ("Trl", SE3)]
+
+
+class PoseOptTrace(C.Structure):
+    """ft_pose_opt_trace: per round the iterations, the rejected trials and the last currentChi"""
+    _fields_ = [("iterations", C.c_int * 4), ("rejected", C.c_int * 4), ("chi2", C.c_double * 4)]
 
 
 class FusePoints(C.Structure):
@@ -296,6 +309,7 @@ def lib() -> C.CDLL:
     L.ft_triangulate_new_points.argtypes = [vp, C.POINTER(TriangKeyFrame), NG, i, C.POINTER(TriangKeyFrame), NG, vp, i, i, f, f, vp, vp, vp, vp]
     L.ft_search_and_triangulate.argtypes = [vp, C.POINTER(TriangKeyFrame), NG, i, C.POINTER(TriangKeyFrame), NG, C.POINTER(TriangPair), i, i, i,
                                             i, i, f, f, vp, vp, vp, vp, vp, vp, vp]
+    L.ft_pose_optimization.argtypes = [vp, i, C.POINTER(PoseOptFrame), C.POINTER(SE3), C.POINTER(vp), vp, C.POINTER(PoseOptTrace)]
     L.ft_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseTarget), vp, vp, vp, vp]
     L.ft_search_keyframe_sim3.argtypes = [vp, C.POINTER(FrameView), i, C.POINTER(Sim3Job)]
     L.ft_distinctive_descriptors.argtypes = [vp, i, vp, vp, vp, vp, vp]

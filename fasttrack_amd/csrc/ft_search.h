@@ -561,6 +561,37 @@ int ft_launch_sim3_resolve(hipStream_t st, const FtDevFrame &F, void *arena, con
 // dynamic LDS of the resolution: a taken bit per keypoint (<= FT_INIT_MAX_LDS: 1 228 800 keypoints)
 inline size_t ft_sim3_lds_bytes(int nKeys) { return 4 * (((size_t)nKeys + 31) / 32); }
 
+// Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:814-1114; kernels_pose_opt.hip) for every frame of a call: one workgroup
+// per job, one launch.  One arena as above.  The host gathers a frame's correspondences in keypoint order into edge records
+// (pose_opt.cpp); frames with fewer than three are answered by the host and have no job.
+struct FtPoseEdge {
+    float X[3];    // GetWorldPos()
+    float obs[3];  // kpUn.pt.x, kpUn.pt.y, mvuRight (stereo)
+    float w;       // mvInvLevelSigma2[kpUn.octave]
+    int kind;      // 0 EdgeSE3ProjectXYZOnlyPose (pCamera), 1 ...ToBody (pCamera2, Trl), 2 EdgeStereoSE3ProjectXYZOnlyPose
+};
+struct FtPoseOptJob {
+    unsigned edges;  // FtPoseEdge[nE]
+    unsigned work;   // device only: float chi2[nE] (what the last computeError left, as the classification reads it), then uint8 level[nE]
+    unsigned out;    // FtPoseOptOut
+    unsigned flags;  // uint8[nE]: mvbOutlier of the edges
+    int nE, model, twoCam;  // twoCam: the frame has to-body edges (Nleft != -1): trlQ / trlT are read
+    float cam[8], cam2[8], bf;
+    float q[4], t[3], trlQ[4], trlT[3];
+};
+struct FtPoseOptOut {
+    float q[4], t[3];
+    int ret;
+    int iterations[4], rejected[4];
+    double chi[4];
+};
+struct FtPoseOptCall {
+    uint8_t *arena;
+    unsigned jobs;  // FtPoseOptJob[nJobs]
+    int nJobs;
+};
+int ft_launch_pose_opt(hipStream_t st, const FtPoseOptCall &T);
+
 #ifdef __HIPCC__
 // rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero; host twin of the pair: rot_hist.h
 __device__ __forceinline__ int init_bin(float angle1, float angle2) {

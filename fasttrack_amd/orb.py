@@ -1393,6 +1393,55 @@ def search_and_triangulate(ctx: Context, kf1: TriangKeyFrame, g1: NewPointGeomet
     return out
 
 
+class PoseOptFrame:
+    """What Optimizer::PoseOptimization reads of a Frame (ft_pose_opt_frame): N keypoints, nleft (-1: one camera), has_point [N]
+    (mvpMapPoints[i] != NULL), world_pos [N, 3], keys (KP_DTYPE: mvKeysUn, or mvKeys of the left camera), keys_right (mvKeysRight)
+    or None, uright [N] or None, inv_level_sigma2, the camera model with the parameters of both cameras, mbf, Tcw and Trl as (q, t)
+    or SE3.  outlier: mvbOutlier as it is before the call (zeros by default).  pinned: a Context - the arrays are copied into
+    pinned host memory of it.  Owns the arrays."""
+
+    def __init__(self, N, nleft, has_point, world_pos, keys, keys_right, uright, inv_level_sigma2, cam_model, cam, cam2, mbf, Tcw, Trl=None,
+                 outlier=None, pinned=None):
+        f32 = np.float32
+        self.has_point = _pinned_copy(pinned, np.asarray(has_point, np.uint8).reshape(-1), np.uint8)
+        self.world_pos = _pinned_copy(pinned, np.asarray(world_pos, f32).reshape(-1, 3), f32)
+        self.keys = _pinned_copy(pinned, keys, _capi.KP_DTYPE)
+        self.keys_right = None if keys_right is None else _pinned_copy(pinned, keys_right, _capi.KP_DTYPE)
+        self.uright = None if uright is None else _pinned_copy(pinned, uright, f32)
+        self.inv_level_sigma2 = np.ascontiguousarray(inv_level_sigma2, f32)
+        self.outlier = np.zeros(max(int(N), 1), np.uint8) if outlier is None else np.ascontiguousarray(outlier, np.uint8).copy()
+        as_se3 = lambda T: T if isinstance(T, SE3) else SE3(T[0], T[1])
+        self.Tcw = as_se3(Tcw)
+        c = _capi.PoseOptFrame()
+        c.N, c.Nleft, c.nlevels, c.cam_model, c.mbf = int(N), int(nleft), len(self.inv_level_sigma2), int(cam_model), float(f32(mbf))
+        c.has_point, c.world_pos, c.keys = ptr(self.has_point), ptr(self.world_pos), ptr(self.keys)
+        c.keys_right = None if self.keys_right is None else ptr(self.keys_right)
+        c.uright = None if self.uright is None else ptr(self.uright)
+        c.inv_level_sigma2 = ptr(self.inv_level_sigma2)
+        c.cam[:] = [float(v) for v in np.asarray(cam, f32)]
+        c.cam2[:] = [float(v) for v in np.asarray(cam if cam2 is None else cam2, f32)]
+        c.Tcw = self.Tcw.c
+        if Trl is not None:
+            c.Trl = as_se3(Trl).c
+        self.c = c
+
+
+def pose_optimization(ctx: Context, frames, trace=True):
+    """Optimizer::PoseOptimization (src/Optimizer.cc:814-1114) for every PoseOptFrame of `frames` in one launch
+    (ft_pose_optimization) -> per frame dict(Tcw = (q [4] xyzw, t [3]) float32, outlier [N] uint8 = mvbOutlier, ret =
+    nInitialCorrespondences - nBad, trace = [(iterations, rejected trials, currentChi)] * 4 or None)"""
+    n = len(frames)
+    F = (_capi.PoseOptFrame * max(n, 1))(*[f.c for f in frames])
+    T = (_capi.SE3 * max(n, 1))()
+    outs = [f.outlier.copy() for f in frames]
+    O = (C.c_void_p * max(n, 1))(*[ptr(o) for o in outs])
+    ret = np.zeros(max(n, 1), np.int32)
+    tr = (_capi.PoseOptTrace * max(n, 1))() if trace else None
+    check(lib().ft_pose_optimization(ctx._h, n, F, T, O, ptr(ret), tr))
+    return [dict(Tcw=(np.array(T[f].q[:], np.float32), np.array(T[f].t[:], np.float32)), outlier=outs[f][:frames[f].c.N], ret=int(ret[f]),
+                 trace=[(tr[f].iterations[r], tr[f].rejected[r], tr[f].chi2[r]) for r in range(4)] if trace else None) for f in range(n)]
+
+
 def inv_level_sigma2(scale_factors):
     """mvInvLevelSigma2 as ORBextractor builds it: 1.0f / (mvScaleFactor[i] * mvScaleFactor[i])"""
     sf = np.asarray(scale_factors, np.float32)

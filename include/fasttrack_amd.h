@@ -915,6 +915,57 @@ FT_API int ft_search_and_triangulate(ft_context *ctx, const ft_triang_keyframe *
                                      int *best_dist /* may be NULL */, int *status, float *x3d, int *n_points, int *first_neighbour);
 
 /* ------------------------------------------------------------------------------------------------
+ * Optimizer::PoseOptimization(Frame *pFrame) (src/Optimizer.cc:814-1114): motion-only bundle adjustment, the solver the tracking
+ * thread runs behind SearchByProjection(Cur, Last) (src/Tracking.cc:2989), SearchByBoW (TrackReferenceKeyFrame), SearchLocalPoints
+ * (:3080) and up to three times per candidate in Relocalization.  n_frames INDEPENDENT frames per call, all of them in ONE launch
+ * (a workgroup per frame): the four rounds, g2o's Levenberg-Marquardt inside each (at most 10 iterations of at most 10 trials),
+ * the outlier classification between the rounds.  No host round trip inside, no CPU path.
+ *
+ * The call reproduces, per frame: the edges in keypoint-index order (:858-993) - a mono edge where uright < 0 (or uright == NULL),
+ * a stereo edge otherwise; with two cameras (Nleft != -1) a left edge for i < Nleft and a to-body edge of the right camera behind
+ * it; nInitialCorrespondences < 3 returns 0 and leaves the pose (mvbOutlier of the correspondences is cleared: the reference
+ * clears it while it builds the edges, in front of that return); errors, Jacobians, the quadratic form with the Huber kernel
+ * (float delta, float dsqr), computeLambdaInit, the rho / _ni / _nBad bookkeeping, SE3Quat::exp with its small-angle branch; every
+ * round restarts from the INPUT pose; an outlier's error is recomputed at the final estimate while an inlier's chi2 is what the
+ * last evaluated estimate left (the rejected one when the run ended on a rejected trial); float thresholds 5.991 / 7.815 against a
+ * float chi2; the robust kernel dropped behind the classification of round 2; the `< 10` break on ALL edges.  All arithmetic in
+ * double, the sums over the edges sequential in keypoint order (g2o's order).  The outlier sweep behind the call
+ * (Tracking.cc:2992-3020) stays with the caller.  Not the reference's: the 6 x 6 LDLT does not pivot (a factor that is not > 0
+ * makes the trial's chi2 DBL_MAX), and sin / cos / atan2 of doubles are fdlibm's kernels (<= 1 ulp off glibc's); DESIGN.md section 4.
+ *
+ * Outputs per frame: Tcw_out[f], the float pose of :1109-1111 (w >= 0); outlier[f][i] = mvbOutlier[i] for the i with has_point,
+ * untouched elsewhere; n_inliers[f] = nInitialCorrespondences - nBad; trace[f] (NULL: none) per round the iterations optimize()
+ * ran, the rejected trials and the last currentChi (0 for a round that did not run).
+ * FT_ERR_INVALID: null arrays, N outside [0, 2^24), Nleft outside -1 / [0, N], nlevels outside [1, 12], an unknown camera model,
+ * the octave of a correspondence outside [0, nlevels), Tcw.q (Trl.q with two cameras) not a unit quaternion, n_frames < 0.
+ * FT_ERR_CAPACITY: a frame with more than FT_POSE_OPT_MAX_EDGES correspondences.  Nothing is written on an error.
+ * ---------------------------------------------------------------------------------------------- */
+#define FT_POSE_OPT_MAX_EDGES 2000
+typedef struct ft_pose_opt_frame {
+    int N;                          /* Frame::N */
+    int Nleft;                      /* Frame::Nleft, -1 = !mpCamera2 */
+    const uint8_t *has_point;       /* [N] mvpMapPoints[i] != NULL */
+    const float *world_pos;         /* N x 3 GetWorldPos(); read where has_point */
+    const ft_keypoint *keys;        /* Nleft == -1: mvKeysUn [N]; else mvKeys [Nleft].  pt and octave are read */
+    const ft_keypoint *keys_right;  /* mvKeysRight [N - Nleft]; read when Nleft != -1 */
+    const float *uright;            /* [N] mvuRight, or NULL: no stereo keypoints; read when Nleft == -1 */
+    const float *inv_level_sigma2;  /* [nlevels] mvInvLevelSigma2 */
+    int nlevels;
+    int cam_model;                  /* 0 Pinhole, 1 KannalaBrandt8: mpCamera and mpCamera2 */
+    float cam[8], cam2[8];          /* their parameters; a stereo edge reads cam[0..3] as fx, fy, cx, cy */
+    float mbf;
+    ft_se3 Tcw;                     /* GetPose() */
+    ft_se3 Trl;                     /* GetRelativePoseTrl(); read when Nleft != -1 */
+} ft_pose_opt_frame;
+typedef struct ft_pose_opt_trace {
+    int iterations[4], rejected[4];
+    double chi2[4];
+} ft_pose_opt_trace;
+FT_API int ft_pose_optimization(ft_context *ctx, int n_frames, const ft_pose_opt_frame *frames /* [n_frames] */,
+                                ft_se3 *Tcw_out /* [n_frames] */, uint8_t *const *outlier /* [n_frames] of [N] */,
+                                int *n_inliers /* [n_frames] */, ft_pose_opt_trace *trace /* [n_frames] or NULL */);
+
+/* ------------------------------------------------------------------------------------------------
  * ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, th, bRight) (src/ORBmatcher.cc:1247-1437) and
  * ORBmatcher::Fuse(KeyFrame *pKF, Sophus::Sim3f &Scw, vpPoints, th, vpReplacePoint) (:1439-1554): the searches
  * LocalMapping::SearchInNeighbors runs for each of its 20 - 40 target keyframes and both cameras, then for the current keyframe

@@ -744,6 +744,27 @@ inline std::vector<std::vector<NewMapPoint>> SearchAndTriangulate(Context &ctx, 
     return detail::newMapPoints(nn, n1, matches12, status, x3d);
 }
 
+// Optimizer::PoseOptimization(Frame *pFrame) (src/Optimizer.cc:814-1114) for a batch of independent frames in one launch
+// (ft_pose_optimization).  vFrames: what the optimisation reads of each Frame; mvbOutlier[f] is resized to the frame's N (new
+// entries false) and keeps its entries without a map point; vPoses[f] is the optimised pose (pFrame->SetPose).  Returns per frame
+// nInitialCorrespondences - nBad.  The sweep behind the call (src/Tracking.cc:2992-3020) stays with the caller.
+inline std::vector<int> PoseOptimization(Context &ctx, const std::vector<ft_pose_opt_frame> &vFrames, std::vector<ft_se3> &vPoses,
+                                         std::vector<std::vector<uint8_t>> &mvbOutlier, std::vector<ft_pose_opt_trace> *trace = nullptr) {
+    const size_t n = vFrames.size();
+    vPoses.resize(n);
+    mvbOutlier.resize(n);
+    std::vector<uint8_t *> flags(n + 1, nullptr);
+    for (size_t f = 0; f < n; f++) {
+        mvbOutlier[f].resize(vFrames[f].N > 0 ? (size_t)vFrames[f].N : 0, 0);
+        flags[f] = mvbOutlier[f].data();
+    }
+    std::vector<int> inliers(n + 1, 0);
+    if (trace) trace->assign(n, ft_pose_opt_trace{});
+    check(ft_pose_optimization(ctx.handle(), (int)n, vFrames.data(), vPoses.data(), flags.data(), inliers.data(), trace ? trace->data() : nullptr));
+    inliers.resize(n);
+    return inliers;
+}
+
 // ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) (src/ORBmatcher.cc:1247-1437) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)
 // (:1439-1554) for one list of map points against every target (keyframe, camera) of LocalMapping::SearchInNeighbors or
 // LoopClosing::SearchAndFuse in one call (ft_fuse_search).  vpMapPoints are the arrays of the points, vTargets one record per
