@@ -285,11 +285,9 @@ int ft_bow_transform(ft_vocabulary *v, const uint8_t *descriptors, int n, int on
 
 }  // extern "C"
 
-// ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (src/ORBmatcher.cc:322-524): the matching inside the common
-// nodes on the device (k_search_by_bow), the rotation-consistency filter (:489-521, ComputeThreeMaxima :2210-2251) here on the
-// downloaded assignments - the order inside a histogram bin does not matter to it, only the bins' sizes.
-// (shared with ft_search_by_bow_keyframes, bow_kf_search.cpp, which passes its own name as `fn`)
-int checkBowSide(const ft_bow_side *s, const char *who, const char *fn) {
+// One ft_bow_side: its check, its place in a call's arena and its staging (search_host.h), for ft_search_by_bow below and the
+// batched calls (bow_kf_search.cpp, bow_cand_search.cpp), which pass their own names as `fn` and ask for `unique`.
+int checkBowSide(const ft_bow_side *s, const char *who, const char *fn, bool unique) {
     auto bad = [&](const char *what) {
         ft_set_error(std::string(fn) + ": " + who + ": " + what);
         return FT_ERR_INVALID;
@@ -297,39 +295,33 @@ int checkBowSide(const ft_bow_side *s, const char *who, const char *fn) {
     if (s->n < 0 || s->n >= (1 << 20) || s->n_nodes < 0) return bad("count out of range");
     if (s->n_nodes > 0 && (!s->fv_nodes || !s->fv_offsets)) return bad("null feature vector");
     if (s->n > 0 && !s->descriptors) return bad("null descriptors");
-    if (s->n_nodes == 0) return FT_OK;
-    if (s->fv_offsets[0] != 0) return bad("fv_offsets[0] != 0");
-    for (int j = 0; j < s->n_nodes; j++) {
-        if (s->fv_offsets[j + 1] < s->fv_offsets[j]) return bad("fv_offsets not ascending");
-        if (j > 0 && s->fv_nodes[j] <= s->fv_nodes[j - 1]) return bad("fv_nodes not strictly ascending");
-    }
-    const int total = s->fv_offsets[s->n_nodes];
-    if (total > s->n) return bad("more feature-vector entries than features");
-    if (total > 0 && !s->fv_features) return bad("null fv_features");
-    for (int e = 0; e < total; e++)
-        if (s->fv_features[e] >= (unsigned)s->n) return bad("feature index out of range");
-    return FT_OK;
+    const char *what = checkFv(fvOf(*s), unique);
+    return what ? bad(what) : FT_OK;
 }
 
-// one side of ft_search_by_bow in the call's arena, and its device view once it is staged in the arena's pinned mirror
-struct BowSideLayout { size_t nodes, offsets, features, desc; };
-static BowSideLayout layoutBowSide(Arena &a, const ft_bow_side *s) {
+BowSideLayout layoutBowSide(Arena &a, const ft_bow_side *s, bool has, bool desc, bool angles) {
     BowSideLayout L;
-    L.nodes = a.take(sizeof(unsigned) * (size_t)s->n_nodes);
-    L.offsets = a.take(sizeof(int) * ((size_t)s->n_nodes + 1));
-    L.features = a.take(sizeof(unsigned) * (size_t)std::max(s->fv_offsets[s->n_nodes], 1));
-    L.desc = a.take((size_t)32 * s->n);
+    const size_t n = (size_t)std::max(s->n, 1);
+    L.fv = layoutFv(a, fvOf(*s));
+    L.desc = desc ? a.take(32 * n) : 0;
+    L.hasPoint = has ? a.take(n) : 0;
+    L.angles = angles ? a.take(4 * n) : 0;
     return L;
 }
-static FtBowSide stageBowSide(const ft_bow_side *s, const BowSideLayout &L, uint8_t *pin, uint8_t *dev) {
-    memcpy(pin + L.nodes, s->fv_nodes, sizeof(unsigned) * (size_t)s->n_nodes);
-    memcpy(pin + L.offsets, s->fv_offsets, sizeof(int) * ((size_t)s->n_nodes + 1));
-    memcpy(pin + L.features, s->fv_features, sizeof(unsigned) * (size_t)s->fv_offsets[s->n_nodes]);
-    memcpy(pin + L.desc, s->descriptors, (size_t)32 * s->n);
-    return FtBowSide{s->n, s->n_nodes, (const unsigned *)(dev + L.nodes), (const int *)(dev + L.offsets),
-                     (const unsigned *)(dev + L.features), dev + L.desc};
+
+FtBowArenaSide stageBowSide(const ft_bow_side *s, const uint8_t *has, const BowSideLayout &L, uint8_t *pin) {
+    const size_t n = (size_t)s->n;
+    if (n) {
+        if (L.desc) memcpy(pin + L.desc, s->descriptors, 32 * n);
+        if (L.hasPoint) memcpy(pin + L.hasPoint, has, n);
+        if (L.angles) memcpy(pin + L.angles, s->angles, 4 * n);
+    }
+    return FtBowArenaSide{stageFv(fvOf(*s), L.fv, pin), -1, s->n, (unsigned)L.desc, (unsigned)L.hasPoint, (unsigned)L.angles};
 }
 
+// ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (src/ORBmatcher.cc:322-524): the matching inside the common
+// nodes on the device (k_search_by_bow), the rotation-consistency filter (:489-521, ComputeThreeMaxima :2210-2251) here on the
+// downloaded assignments - the order inside a histogram bin does not matter to it, only the bins' sizes.
 int ft_search_by_bow(ft_context *ctx, const ft_bow_side *kf, const uint8_t *kf_has_point, const ft_bow_side *frame, int frame_nleft,
                      float nn_ratio, int check_orientation, int *matches, int *n_matches) {
     FT_REQUIRE(ctx && kf && frame && matches, "ft_search_by_bow: null argument");
@@ -347,22 +339,24 @@ int ft_search_by_bow(ft_context *ctx, const ft_bow_side *kf, const uint8_t *kf_h
     rc = ft_set_device(ctx);
     if (rc != FT_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->matchMutex);
-    // one block of the context's scratch: per side nodes | offsets | features | descriptors, then has_point, then matches (-1)
+    // one block of the context's scratch: per side nodes | offsets | features | descriptors, the keyframe's has_point, then matches (-1)
     Arena a;
-    const BowSideLayout Lk = layoutBowSide(a, kf), Lf = layoutBowSide(a, frame);
-    const size_t oHas = a.take((size_t)kf->n);
+    const BowSideLayout Lk = layoutBowSide(a, kf, true, true, false), Lf = layoutBowSide(a, frame, false, true, false);
     const size_t oMatches = a.take(sizeof(int) * (size_t)N);
     rc = ft_ensure_scratch(ctx, a.off, a.off);
     if (rc != FT_OK) return rc;
     uint8_t *dev = (uint8_t *)ctx->scratchDev, *pin = (uint8_t *)ctx->scratchPin;
     hipStream_t st = ctx->stream;
-    const FtBowSide Dk = stageBowSide(kf, Lk, pin, dev), Df = stageBowSide(frame, Lf, pin, dev);
-    memcpy(pin + oHas, kf_has_point, (size_t)kf->n);
+    auto pointers = [&](const FtBowArenaSide &D) {
+        return FtBowSide{D.fv.n, D.fv.nNodes, (const unsigned *)(dev + D.fv.nodes), (const int *)(dev + D.fv.offsets),
+                         (const unsigned *)(dev + D.fv.feats), dev + D.desc};
+    };
+    const FtBowSide Dk = pointers(stageBowSide(kf, kf_has_point, Lk, pin)), Df = pointers(stageBowSide(frame, nullptr, Lf, pin));
     memset(pin + oMatches, 0xff, sizeof(int) * (size_t)N);
     CallEventTimer own;
     CallScope C{ctx, st, dev, pin, own.evt};
     C.up(0, a.off);  // one copy: the block is contiguous
-    C.launch(nullptr, [&] { return ft_launch_search_by_bow(st, Dk, dev + oHas, Df, frame_nleft, nn_ratio, (int *)(dev + oMatches)); });
+    C.launch(nullptr, [&] { return ft_launch_search_by_bow(st, Dk, dev + Lk.hasPoint, Df, frame_nleft, nn_ratio, (int *)(dev + oMatches)); });
     rc = C.down(oMatches, oMatches + sizeof(int) * (size_t)N);
     if (rc != FT_OK) return rc;
     memcpy(matches, pin + oMatches, sizeof(int) * (size_t)N);

@@ -7,56 +7,7 @@
 
 #include "search_host.h"
 
-namespace {
-
-const char *const FN = "ft_search_by_bow_candidates";
-
-struct SideLayout {
-    size_t nodes, offsets, feats, desc, hasPoint, angles;
-    int total;  // FeatureVector entries
-};
-
-// has: the side's has_point, null for the frame; desc: whether the side's descriptors are staged in the arena
-SideLayout layoutSide(Arena &a, const ft_bow_side *s, bool has, bool desc, bool angles) {
-    SideLayout L;
-    const size_t n = (size_t)std::max(s->n, 1), nn = (size_t)s->n_nodes;
-    L.total = s->n_nodes ? s->fv_offsets[s->n_nodes] : 0;
-    L.nodes = a.take(4 * std::max(nn, (size_t)1));
-    L.offsets = a.take(4 * (nn + 1));
-    L.feats = a.take(4 * (size_t)std::max(L.total, 1));
-    L.desc = desc ? a.take(32 * n) : 0;
-    L.hasPoint = has ? a.take(n) : 0;
-    L.angles = angles ? a.take(4 * n) : 0;
-    return L;
-}
-
-FtBowCandSide stageSide(const ft_bow_side *s, const uint8_t *has, bool desc, const SideLayout &L, bool angles, uint8_t *pin) {
-    const size_t n = (size_t)s->n, nn = (size_t)s->n_nodes;
-    if (n) {
-        if (desc) memcpy(pin + L.desc, s->descriptors, 32 * n);
-        if (has) memcpy(pin + L.hasPoint, has, n);
-        if (angles) memcpy(pin + L.angles, s->angles, 4 * n);
-    }
-    if (nn) {
-        memcpy(pin + L.nodes, s->fv_nodes, 4 * nn);
-        memcpy(pin + L.offsets, s->fv_offsets, 4 * (nn + 1));
-        if (L.total) memcpy(pin + L.feats, s->fv_features, 4 * (size_t)L.total);
-    } else {
-        memset(pin + L.offsets, 0, 4);
-    }
-    FtBowCandSide D;
-    D.n = s->n;
-    D.nNodes = s->n_nodes;
-    D.nodes = (unsigned)L.nodes;
-    D.offsets = (unsigned)L.offsets;
-    D.feats = (unsigned)L.feats;
-    D.desc = (unsigned)L.desc;
-    D.hasPoint = (unsigned)L.hasPoint;
-    D.angles = (unsigned)L.angles;
-    return D;
-}
-
-}  // namespace
+static const char *const FN = "ft_search_by_bow_candidates";
 
 extern "C" {
 
@@ -66,19 +17,12 @@ int ft_search_by_bow_candidates(ft_context *ctx, const ft_bow_side *frame, int f
     FT_REQUIRE(n_keyframes >= 0 && n_keyframes < (1 << 16), "ft_search_by_bow_candidates: n_keyframes out of range");
     FT_REQUIRE(n_keyframes == 0 || (keyframes && n_matches), "ft_search_by_bow_candidates: null keyframes or n_matches");
     const bool ori = check_orientation != 0, resident = frame_descriptors_on_device != 0;
-    int rc = checkBowSide(frame, "frame", FN);
+    // a frame feature sits under one node: what makes the nodes, and with them the waves of a candidate, independent
+    int rc = checkBowSide(frame, "frame", FN, true);
     if (rc != FT_OK) return rc;
     const int N = frame->n;
     FT_REQUIRE(frame_nleft >= -1 && frame_nleft <= N, "ft_search_by_bow_candidates: frame_nleft out of range");
     FT_REQUIRE(!ori || N == 0 || frame->angles, "ft_search_by_bow_candidates: frame: check_orientation needs the keypoint angles");
-    {   // a frame feature sits under one node: what makes the nodes, and with them the waves of a candidate, independent
-        std::vector<uint8_t> seen((size_t)N, 0);
-        const int total = frame->n_nodes ? frame->fv_offsets[frame->n_nodes] : 0;
-        for (int e = 0; e < total; e++) {
-            FT_REQUIRE(!seen[frame->fv_features[e]], "ft_search_by_bow_candidates: frame: a feature is listed twice");
-            seen[frame->fv_features[e]] = 1;
-        }
-    }
     for (int k = 0; k < n_keyframes; k++) {
         const std::string who = "keyframe [" + std::to_string(k) + "]";
         const ft_bow_side *s = &keyframes[k].side;
@@ -95,9 +39,9 @@ int ft_search_by_bow_candidates(ft_context *ctx, const ft_bow_side *frame, int f
     }
     // the arena: frame side | candidates | jobs | matches (-1) || n_matches
     Arena a;
-    const SideLayout LF = layoutSide(a, frame, false, !resident, ori);
-    std::vector<SideLayout> LK((size_t)n_keyframes);
-    for (int k = 0; k < n_keyframes; k++) LK[k] = layoutSide(a, &keyframes[k].side, true, true, ori);
+    const BowSideLayout LF = layoutBowSide(a, frame, false, !resident, ori);
+    std::vector<BowSideLayout> LK((size_t)n_keyframes);
+    for (int k = 0; k < n_keyframes; k++) LK[k] = layoutBowSide(a, &keyframes[k].side, true, true, ori);
     const size_t oJobs = a.take(sizeof(FtBowCandJob) * (size_t)n_keyframes);
     const size_t rows = 4 * (size_t)N * (size_t)n_keyframes;
     const size_t oMatches = a.take(rows);
@@ -117,14 +61,14 @@ int ft_search_by_bow_candidates(ft_context *ctx, const ft_bow_side *frame, int f
     FtBowCandCall T;
     memset(&T, 0, sizeof T);
     T.arena = dev;
-    T.F = stageSide(frame, nullptr, !resident, LF, ori, pin);
+    T.F = stageBowSide(frame, nullptr, LF, pin);
     T.frameDesc = resident ? frame->descriptors : dev + LF.desc;
     FtBowCandJob *jobs = (FtBowCandJob *)(pin + oJobs);
     for (int k = 0; k < n_keyframes; k++) {
         FtBowCandJob &J = jobs[k];
-        J.K = stageSide(&keyframes[k].side, keyframes[k].has_point, true, LK[k], ori, pin);
+        J.K = stageBowSide(&keyframes[k].side, keyframes[k].has_point, LK[k], pin);
         J.matches = (unsigned)(oMatches + 4 * (size_t)N * k);
-        T.maxNodes = std::max(T.maxNodes, J.K.nNodes);
+        T.maxNodes = std::max(T.maxNodes, J.K.fv.nNodes);
     }
     memset(pin + oMatches, 0xff, rows);  // everything the kernel does not write is -1
     T.jobs = (unsigned)oJobs;

@@ -11,69 +11,23 @@ namespace {
 
 const char *const FN = "ft_search_by_bow_keyframes";
 
-struct SideLayout {
-    size_t nodes, offsets, feats, desc, hasPoint, angles;
-    int total;  // FeatureVector entries
-};
-
-int checkKeyframe(const ft_bow_keyframe *k, const std::string &who, bool needAngles, std::vector<uint8_t> &seen) {
+int checkKeyframe(const ft_bow_keyframe *k, const std::string &who, bool needAngles) {
     const ft_bow_side *s = &k->side;
-    int rc = checkBowSide(s, who.c_str(), FN);
+    int rc = checkBowSide(s, who.c_str(), FN, true);  // a FeatureVector holds a feature under one node
     if (rc != FT_OK) return rc;
     const std::string w = std::string(FN) + ": " + who + ": ";
     FT_REQUIRE(s->n == 0 || k->has_point, w + "null has_point");
     FT_REQUIRE(k->n_left >= -1 && k->n_left <= s->n, w + "n_left out of range");
     FT_REQUIRE(k->n_left == -1 || (k->n_un >= 0 && k->n_un <= s->n), w + "n_un out of range");
     FT_REQUIRE(!needAngles || s->n == 0 || s->angles, w + "check_orientation needs the keypoint angles");
-    const int total = s->n_nodes ? s->fv_offsets[s->n_nodes] : 0;
-    seen.assign((size_t)s->n, 0);
-    for (int e = 0; e < total; e++) {
-        FT_REQUIRE(!seen[s->fv_features[e]], w + "a feature is listed twice");  // a FeatureVector holds a feature under one node
-        seen[s->fv_features[e]] = 1;
-    }
     return FT_OK;
 }
 
-SideLayout layoutSide(Arena &a, const ft_bow_keyframe *k, bool angles) {
-    const ft_bow_side *s = &k->side;
-    SideLayout L;
-    const size_t n = (size_t)std::max(s->n, 1), nn = (size_t)s->n_nodes;
-    L.total = s->n_nodes ? s->fv_offsets[s->n_nodes] : 0;
-    L.nodes = a.take(4 * std::max(nn, (size_t)1));
-    L.offsets = a.take(4 * (nn + 1));
-    L.feats = a.take(4 * (size_t)std::max(L.total, 1));
-    L.desc = a.take(32 * n);
-    L.hasPoint = a.take(n);
-    L.angles = angles ? a.take(4 * n) : 0;
-    return L;
-}
-
-FtBowKfSide stageSide(const ft_bow_keyframe *k, const SideLayout &L, bool angles, uint8_t *pin) {
-    const ft_bow_side *s = &k->side;
-    const size_t n = (size_t)s->n, nn = (size_t)s->n_nodes;
-    if (n) {
-        memcpy(pin + L.desc, s->descriptors, 32 * n);
-        memcpy(pin + L.hasPoint, k->has_point, n);
-        if (angles) memcpy(pin + L.angles, s->angles, 4 * n);
-    }
-    if (nn) {
-        memcpy(pin + L.nodes, s->fv_nodes, 4 * nn);
-        memcpy(pin + L.offsets, s->fv_offsets, 4 * (nn + 1));
-        if (L.total) memcpy(pin + L.feats, s->fv_features, 4 * (size_t)L.total);
-    } else {
-        memset(pin + L.offsets, 0, 4);
-    }
-    FtBowKfSide D;
-    D.n = s->n;
-    D.nNodes = s->n_nodes;
+// the side of a keyframe: with has_point and descriptors, and what KeyFrame::NLeft / mvKeysUn.size() say of a second camera
+FtBowArenaSide stageKeyframe(const ft_bow_keyframe *k, const BowSideLayout &L, uint8_t *pin) {
+    FtBowArenaSide D = stageBowSide(&k->side, k->has_point, L, pin);
     D.nLeft = k->n_left;
-    D.nUn = k->n_left == -1 ? s->n : k->n_un;
-    D.nodes = (unsigned)L.nodes;
-    D.offsets = (unsigned)L.offsets;
-    D.feats = (unsigned)L.feats;
-    D.desc = (unsigned)L.desc;
-    D.hasPoint = (unsigned)L.hasPoint;
-    D.angles = (unsigned)L.angles;
+    if (k->n_left != -1) D.nUn = k->n_un;
     return D;
 }
 
@@ -87,11 +41,10 @@ int ft_search_by_bow_keyframes(ft_context *ctx, const ft_bow_keyframe *kf1, int 
     FT_REQUIRE(n_keyframes >= 0 && n_keyframes < (1 << 16), "ft_search_by_bow_keyframes: n_keyframes out of range");
     FT_REQUIRE(n_keyframes == 0 || (kf2 && n_matches), "ft_search_by_bow_keyframes: null keyframes or n_matches");
     const bool ori = check_orientation != 0;
-    std::vector<uint8_t> seen;
-    int rc = checkKeyframe(kf1, "keyframe 1", ori, seen);
+    int rc = checkKeyframe(kf1, "keyframe 1", ori);
     if (rc != FT_OK) return rc;
     for (int k = 0; k < n_keyframes; k++) {
-        rc = checkKeyframe(kf2 + k, "keyframe 2 [" + std::to_string(k) + "]", ori, seen);
+        rc = checkKeyframe(kf2 + k, "keyframe 2 [" + std::to_string(k) + "]", ori);
         if (rc != FT_OK) return rc;
     }
     const int n1 = kf1->side.n;
@@ -106,9 +59,9 @@ int ft_search_by_bow_keyframes(ft_context *ctx, const ft_bow_keyframe *kf1, int 
     FtTimer tAll;
     // the arena: keyframe 1 | the keyframes 2 | jobs | claim flags (0) | matches12 (-1) || n_matches
     Arena a;
-    const SideLayout L1 = layoutSide(a, kf1, ori);
-    std::vector<SideLayout> L2((size_t)n_keyframes);
-    for (int k = 0; k < n_keyframes; k++) L2[k] = layoutSide(a, kf2 + k, ori);
+    const BowSideLayout L1 = layoutBowSide(a, &kf1->side, true, true, ori);
+    std::vector<BowSideLayout> L2((size_t)n_keyframes);
+    for (int k = 0; k < n_keyframes; k++) L2[k] = layoutBowSide(a, &kf2[k].side, true, true, ori);
     const size_t oJobs = a.take(sizeof(FtBowKfJob) * (size_t)n_keyframes);
     const size_t oClaimed = a.off;
     std::vector<size_t> oClaim((size_t)n_keyframes);
@@ -127,11 +80,11 @@ int ft_search_by_bow_keyframes(ft_context *ctx, const ft_bow_keyframe *kf1, int 
     FtBowKfCall T;
     memset(&T, 0, sizeof T);
     T.arena = dev;
-    T.K1 = stageSide(kf1, L1, ori, pin);
+    T.K1 = stageKeyframe(kf1, L1, pin);
     FtBowKfJob *jobs = (FtBowKfJob *)(pin + oJobs);
     for (int k = 0; k < n_keyframes; k++) {
         FtBowKfJob &J = jobs[k];
-        J.K2 = stageSide(kf2 + k, L2[k], ori, pin);
+        J.K2 = stageKeyframe(kf2 + k, L2[k], pin);
         J.matches = (unsigned)(oMatches + 4 * (size_t)n1 * k);
         J.claimed = (unsigned)oClaim[k];
     }

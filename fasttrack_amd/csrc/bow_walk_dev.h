@@ -13,29 +13,18 @@
 // and read back by the SAME lane (position & 63), so no ordering between lanes is needed.  matches[] is the row of ONE
 // (keyframe, frame) search, -1 where nothing is assigned: nothing else carries a claim.
 #pragma once
-#include "ft_internal.h"
+#include "ft_search.h"
 #include "wave_ops.h"
 
 // a: the keyframe's node (entry of K.nodes, wave-uniform, < K.nNodes); lane: threadIdx.x & 63
 __device__ __forceinline__ void bow_walk_node(const FtBowSide &K, const uint8_t *kfHasPoint, const FtBowSide &F, int nleft, float nnRatio,
                                               int *matches, int a, int lane) {
     const unsigned node = K.nodes[a];
-    int lo = 0, hi = F.nNodes;  // lower_bound
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (F.nodes[mid] < node) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= F.nNodes || F.nodes[lo] != node) return;
+    const int lo = fv_find_node(F.nodes, F.nNodes, node);
+    if (lo < 0) return;
     const int fBeg = F.offsets[lo], fCnt = F.offsets[lo + 1] - fBeg;
     const int kBeg = K.offsets[a], kEnd = K.offsets[a + 1];
     constexpr unsigned NONE = (256u << 20) | 0xfffffu;  // bestDist = 256, no index
-    auto twoMin = [](unsigned &x0, unsigned &x1) {
-        const unsigned m0 = wave_min_u32(x0);
-        const unsigned m1 = wave_min_u32(x0 == m0 ? x1 : x0);
-        x0 = m0;
-        x1 = m1;
-    };
     constexpr int R = 4;  // frame features per lane held in registers
     if (fCnt <= 64 * R) {
         // The usual node (a few dozen to a few hundred features) lives in registers: lane l holds the node's frame features
@@ -57,10 +46,6 @@ __device__ __forceinline__ void bow_walk_node(const FtBowSide &K, const uint8_t 
             freeMask |= (have ? 1u : 0u) << r;
             rightMask |= ((nleft != -1 && (int)fIdx[r] >= nleft) ? 1u : 0u) << r;
         }
-        auto bcast64 = [](unsigned long long v, int j) {
-            return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), j) << 32) |
-                   (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, j);
-        };
         for (int k0i = kBeg; k0i < kEnd; k0i += 64) {
             const int kCnt = min(64, kEnd - k0i);
             const bool haveK = lane < kCnt;
@@ -72,7 +57,7 @@ __device__ __forceinline__ void bow_walk_node(const FtBowSide &K, const uint8_t 
                 const int j = __builtin_amdgcn_readfirstlane(jj);
                 if (!__builtin_amdgcn_readlane(has, j)) continue;
                 const int kf = __builtin_amdgcn_readlane((int)kIdx, j);
-                const unsigned long long b0 = bcast64(d0, j), b1 = bcast64(d1, j), b2 = bcast64(d2, j), b3 = bcast64(d3, j);
+                const unsigned long long b0 = wave_readlane_u64(d0, j), b1 = wave_readlane_u64(d1, j), b2 = wave_readlane_u64(d2, j), b3 = wave_readlane_u64(d3, j);
                 unsigned l0 = NONE, l1 = NONE, r0 = NONE, r1 = NONE;
 #pragma unroll
                 for (int r = 0; r < R; r++) {
@@ -86,7 +71,7 @@ __device__ __forceinline__ void bow_walk_node(const FtBowSide &K, const uint8_t 
                     r0 = min(r0, keyR);
                     r1 = min(r1, largerR);
                 }
-                twoMin(l0, l1);
+                wave_two_min(l0, l1);
                 if ((int)(l0 >> 20) > 50) continue;
                 auto claim = [&](unsigned key) {
                     const int p = (int)(key & 0xfffffu);
@@ -101,7 +86,7 @@ __device__ __forceinline__ void bow_walk_node(const FtBowSide &K, const uint8_t 
                 };
                 if (__fmul_rn(nnRatio, (float)(l1 >> 20)) > (float)(l0 >> 20)) claim(l0);
                 if (nleft != -1) {
-                    twoMin(r0, r1);
+                    wave_two_min(r0, r1);
                     if ((int)(r0 >> 20) <= 50) claim(r0);
                 }
             }
@@ -132,7 +117,7 @@ __device__ __forceinline__ void bow_walk_node(const FtBowSide &K, const uint8_t 
             r0 = min(r0, keyR);
             r1 = min(r1, largerR);
         }
-        twoMin(l0, l1);
+        wave_two_min(l0, l1);
         const int bestDist1 = (int)(l0 >> 20), bestDist2 = (int)(l1 >> 20);
         if (bestDist1 > 50) continue;  // TH_LOW (:424); the right camera is only looked at inside this branch (:451)
         const int kf = (int)kfIdx;
@@ -141,7 +126,7 @@ __device__ __forceinline__ void bow_walk_node(const FtBowSide &K, const uint8_t 
             if ((p & 63) == lane) __hip_atomic_store(matches + F.features[fBeg + p], kf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (nleft != -1) {
-            twoMin(r0, r1);
+            wave_two_min(r0, r1);
             if ((int)(r0 >> 20) <= 50) {  // the right camera's ratio test is disabled in the reference ("|| true", :453)
                 const int p = (int)(r0 & 0xfffffu);
                 if ((p & 63) == lane) __hip_atomic_store(matches + F.features[fBeg + p], kf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -363,8 +363,8 @@ bool ft_is_pinned_host_range(const void *p, size_t bytes);  // [p, p + bytes) in
 bool ft_host_block_contains(ft_context *ctx, const void *p, size_t bytes);
 int ft_extract_foreign_wait(ft_extractor *ex);  // orders the extractor's next batch behind ex->foreignReader (never inside a stream capture)
 int ft_ensure_scratch(ft_context *ctx, size_t devBytes, size_t pinBytes);  // grow-only matcher scratch (hold matchMutex)
-// counts, null arrays, ascending offsets / nodes and index range of one ft_bow_side (bow.cpp); fn: the entry point the message names
-int checkBowSide(const ft_bow_side *s, const char *who, const char *fn = "ft_search_by_bow");
+// counts, null arrays and the FeatureVector (checkFv, fv_host.h) of one ft_bow_side (bow.cpp); fn: the entry point the message names
+int checkBowSide(const ft_bow_side *s, const char *who, const char *fn = "ft_search_by_bow", bool unique = false);
 int ft_usable_cpus();
 int ft_hw_queues_hint();
 bool ft_parse_lane_map(const char *text, std::vector<int> &map, std::string &err);

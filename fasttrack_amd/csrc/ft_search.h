@@ -3,6 +3,7 @@
 #pragma once
 
 #include "ft_internal.h"
+#include "fv_host.h"
 
 struct FtDevFrame {
     int N, Nleft;
@@ -329,9 +330,9 @@ inline size_t ft_reloc_lds_bytes(int nLeftKeys, int nPoints) { return 4 * (((siz
 // arena pointer it got as an argument.
 #define FT_TRIANG_NONE 0xffffffffu  // FtTriangSide::uright: the keyframe has no mvuRight (all -1)
 struct FtTriangSide {
-    int n, nLeft, nNodes;           // features, KeyFrame::NLeft, FeatureVector entries
+    FtFv fv;                        // features and the FeatureVector in CSR form (fv_host.h)
+    int nLeft;                      // KeyFrame::NLeft
     unsigned keys, desc;            // ft_keypoint[n], n x 32
-    unsigned nodes, offsets, feats; // the FeatureVector in CSR form
     unsigned hasPoint, uright;      // uint8[n], float[n] (or FT_TRIANG_NONE)
     unsigned sf, sigma2;            // mvScaleFactors, mvLevelSigma2
     float cam[2][8];                // mpCamera, mpCamera2
@@ -377,21 +378,23 @@ struct FtNewPointCall {
 // one launch, behind ft_launch_triang_finish or on staged match rows: reads FtTriangJob::matches, FtTriangSide keys / uright / sf / sigma2 / cam
 int ft_launch_triang_points(hipStream_t st, const FtTriangCall &T, const FtNewPointCall &P);
 
-// ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:864-1004; kernels_bow_kf.hip) for keyframe 1 against every
-// neighbour of a call.  One arena as above: records hold byte offsets into it.
-struct FtBowKfSide {
-    int n, nNodes, nLeft, nUn;       // KeyFrame::N, FeatureVector entries, KeyFrame::NLeft, mvKeysUn.size()
-    unsigned nodes, offsets, feats;  // the FeatureVector in CSR form
-    unsigned desc, hasPoint, angles; // n x 32, uint8[n], float[n] (angles only with checkOrientation)
+// One side of the batched SearchByBoW calls below in the arena of its call (stageBowSide, bow.cpp): records hold byte offsets into it.
+// A side without a second camera - the frame of the candidate call among them - has nLeft = -1, nUn = n.
+struct FtBowArenaSide {
+    FtFv fv;                         // features and the FeatureVector in CSR form (fv_host.h)
+    int nLeft, nUn;                  // KeyFrame::NLeft, mvKeysUn.size()
+    unsigned desc, hasPoint, angles; // n x 32, uint8[n], float[n] (angles only with checkOrientation; 0 = not staged)
 };
+// ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:864-1004; kernels_bow_kf.hip) for keyframe 1 against every
+// neighbour of a call.  One arena as above.
 struct FtBowKfJob {  // one neighbour
-    FtBowKfSide K2;
+    FtBowArenaSide K2;
     unsigned matches;  // int[K1.n], -1 from the host's fill
     unsigned claimed;  // int[K2.n], 0 from the host's fill: vbMatched2 of the lists too long for the registers
 };
 struct FtBowKfCall {
     uint8_t *arena;
-    FtBowKfSide K1;
+    FtBowArenaSide K1;
     unsigned jobs;      // FtBowKfJob[nNeighbours]
     unsigned nMatches;  // int[nNeighbours]
     int nNeighbours, checkOrientation;
@@ -404,19 +407,14 @@ int ft_launch_bow_kf_finish(hipStream_t st, const FtBowKfCall &T);
 // ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (src/ORBmatcher.cc:322-524; kernels_bow_cand.hip) for one frame against every
 // candidate keyframe of a call (Tracking::Relocalization, src/Tracking.cc:3839-3860).  One arena as above; the frame's descriptors
 // alone are a pointer, because they may be read where a front end left them.
-struct FtBowCandSide {
-    int n, nNodes;                   // features, FeatureVector entries
-    unsigned nodes, offsets, feats;  // the FeatureVector in CSR form
-    unsigned desc, hasPoint, angles; // n x 32, uint8[n], float[n] (angles only with checkOrientation; the frame has no hasPoint)
-};
 struct FtBowCandJob {  // one candidate keyframe
-    FtBowCandSide K;
+    FtBowArenaSide K;
     unsigned matches;  // int[F.n], -1 from the host's fill: the job's row, which also carries its claims
 };
 struct FtBowCandCall {
     uint8_t *arena;
     const uint8_t *frameDesc;  // F.n x 32: arena + F.desc, or the caller's device pointer
-    FtBowCandSide F;
+    FtBowArenaSide F;          // (the frame has no hasPoint)
     unsigned jobs;      // FtBowCandJob[nCandidates]
     unsigned nMatches;  // int[nCandidates]
     int nCandidates, maxNodes;  // maxNodes: the largest K.nNodes of the call (the grid's x extent in waves)
@@ -593,7 +591,8 @@ struct FtPoseOptCall {
 int ft_launch_pose_opt(hipStream_t st, const FtPoseOptCall &T);
 
 #ifdef __HIPCC__
-// rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero; host twin of the pair: rot_hist.h
+// rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero; host twin of the pair: rot_hist.h,
+// the filter of a workgroup over them: rot_filter_dev.h
 __device__ __forceinline__ int init_bin(float angle1, float angle2) {
     float rot = __fsub_rn(angle1, angle2);
     if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
@@ -642,6 +641,23 @@ __device__ __forceinline__ Window cell_window(const FtDevFrame &F, float x, floa
     w.maxCY = min(FT_GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F.mnMinY), r), F.invH)));
     if (w.maxCY < 0) w.empty = true;
     return w;
+}
+
+// what a record's byte offset names in the arena of its call
+template <class T>
+__device__ __forceinline__ const T *at(const uint8_t *arena, unsigned off) {
+    return (const T *)(arena + off);
+}
+// the entry of `node` in the ascending node ids of a FeatureVector (the reference's lower_bound walk over two FeatureVectors
+// visits exactly the common keys), or -1
+__device__ __forceinline__ int fv_find_node(const unsigned *nodes, int nNodes, unsigned node) {
+    int lo = 0, hi = nNodes;  // lower_bound
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (nodes[mid] < node) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < nNodes && nodes[lo] == node ? lo : -1;
 }
 
 // Re-derives a pointer read from a job record from the arena pointer the kernel got as an argument (FramePtrs, search_dev.h: a

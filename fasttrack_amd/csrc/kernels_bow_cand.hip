@@ -19,72 +19,34 @@
 #include "bow_walk_dev.h"
 #include "ft_internal.h"
 #include "ft_search.h"
+#include "rot_filter_dev.h"
 #include "wave_ops.h"
 
 namespace {
 
 #define FT_BOWCAND_FIN_T 256
 
-template <class T>
-__device__ __forceinline__ const T *at(const uint8_t *arena, unsigned off) {
-    return (const T *)(arena + off);
-}
-
 __global__ __launch_bounds__(256) void k_bow_cand_match(FtBowCandCall T) {
     const uint8_t *arena = T.arena;
     const int lane = threadIdx.x & 63;
     const int a = (int)blockIdx.x * 4 + wave_index();
     const FtBowCandJob *job = at<FtBowCandJob>(arena, T.jobs) + blockIdx.y;
-    const int n = job->K.n, nNodes = job->K.nNodes;
+    const int n = job->K.fv.n, nNodes = job->K.fv.nNodes;
     if (a >= nNodes || n <= 0) return;  // nothing of an empty candidate is dereferenced
-    const FtBowSide K{n, nNodes, at<unsigned>(arena, job->K.nodes), at<int>(arena, job->K.offsets), at<unsigned>(arena, job->K.feats),
+    const FtBowSide K{n, nNodes, at<unsigned>(arena, job->K.fv.nodes), at<int>(arena, job->K.fv.offsets), at<unsigned>(arena, job->K.fv.feats),
                       arena + job->K.desc};
-    const FtBowSide F{T.F.n, T.F.nNodes, at<unsigned>(arena, T.F.nodes), at<int>(arena, T.F.offsets), at<unsigned>(arena, T.F.feats),
+    const FtBowSide F{T.F.fv.n, T.F.fv.nNodes, at<unsigned>(arena, T.F.fv.nodes), at<int>(arena, T.F.fv.offsets), at<unsigned>(arena, T.F.fv.feats),
                       T.frameDesc};
     bow_walk_node(K, arena + job->K.hasPoint, F, T.nLeft, T.nnRatio, (int *)(T.arena + job->matches), a, lane);
 }
 
 __global__ __launch_bounds__(FT_BOWCAND_FIN_T) void k_bow_cand_finish(FtBowCandCall T) {
-    __shared__ int hist[FT_HISTO_LENGTH];
-    __shared__ int keepBits, total;
     uint8_t *arena = T.arena;
-    const int tid = threadIdx.x, lane = tid & 63;
     const FtBowCandJob *job = at<FtBowCandJob>(arena, T.jobs) + blockIdx.x;
-    int *matches = (int *)(arena + job->matches);
     const float *angleKf = at<float>(arena, job->K.angles), *angleF = at<float>(arena, T.F.angles);
-    const int n = T.F.n;
-    if (tid < FT_HISTO_LENGTH) hist[tid] = 0;
-    if (tid == 0) total = 0;
-    __syncthreads();
-    if (T.checkOrientation) {
-        for (int i = tid; i < n; i += FT_BOWCAND_FIN_T) {
-            const int m = matches[i];
-            if (m < 0) continue;
-            const int bin = init_bin(angleKf[m], angleF[i]);  // kp.angle - Fkp.angle (:491): the keyframe's minus the frame's
-            if (bin >= 0 && bin < FT_HISTO_LENGTH) atomicAdd(&hist[bin], 1);  // (the reference asserts)
-        }
-        __syncthreads();
-        if (tid == 0) keepBits = three_maxima_keep(hist);
-        __syncthreads();
-    }
-    const int keep = T.checkOrientation ? keepBits : -1;
-    int nm = 0;
-    for (int i = tid; i < n; i += FT_BOWCAND_FIN_T) {
-        const int m = matches[i];
-        if (m < 0) continue;
-        if (T.checkOrientation) {
-            const int bin = init_bin(angleKf[m], angleF[i]);
-            if (bin >= 0 && bin < FT_HISTO_LENGTH && !((keep >> bin) & 1)) {  // :509-519
-                matches[i] = -1;
-                continue;
-            }
-        }
-        nm++;
-    }
-    nm = wave_sum_i32(nm);
-    if (lane == 0 && nm) atomicAdd(&total, nm);
-    __syncthreads();
-    if (tid == 0) ((int *)(arena + T.nMatches))[blockIdx.x] = total;
+    // kp.angle - Fkp.angle (:491): the keyframe's minus the frame's, and the row is the frame's; the removal :509-519
+    rot_filter_rows<FT_BOWCAND_FIN_T>((int *)(arena + job->matches), T.F.fv.n, T.checkOrientation, (int *)(arena + T.nMatches) + blockIdx.x,
+                                      [&](int i, int m) { return init_bin(angleKf[m], angleF[i]); });
 }
 
 }  // namespace

@@ -34,17 +34,13 @@
 
 #include "ft_internal.h"
 #include "ft_search.h"
+#include "rot_filter_dev.h"
 #include "wave_ops.h"
 
 namespace {
 
 #define FT_BOWKF_R 4  // candidates per lane held in registers: lists of up to 64 * FT_BOWKF_R entries
 #define FT_BOWKF_FIN_T 256
-
-template <class T>
-__device__ __forceinline__ const T *at(const uint8_t *arena, unsigned off) {
-    return (const T *)(arena + off);
-}
 
 // !(NLeft != -1 && idx >= mvKeysUn.size()) && pMP && !pMP->isBad()  (:899-907 for keyframe 1, :919-929 for keyframe 2)
 __device__ __forceinline__ bool eligible(int nLeft, int nUn, const uint8_t *has, unsigned idx) {
@@ -56,24 +52,17 @@ __global__ __launch_bounds__(256) void k_bow_kf_match(FtBowKfCall T) {
     uint8_t *arena = T.arena;
     const int lane = threadIdx.x & 63;
     const int a = (int)blockIdx.x * 4 + wave_index();
-    const FtBowKfSide &K1 = T.K1;
-    if (a >= K1.nNodes) return;
+    const FtBowArenaSide &K1 = T.K1;
+    if (a >= K1.fv.nNodes) return;
     const FtBowKfJob *job = at<FtBowKfJob>(arena, T.jobs) + blockIdx.y;
-    const FtBowKfSide K2 = job->K2;
-    if (K2.n <= 0 || K2.nNodes <= 0) return;  // nothing of an empty neighbour is dereferenced
-    const unsigned node = at<unsigned>(arena, K1.nodes)[a];
-    const unsigned *nodes2 = at<unsigned>(arena, K2.nodes);
-    int lo = 0, hi = K2.nNodes;  // lower_bound
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (nodes2[mid] < node) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= K2.nNodes || nodes2[lo] != node) return;
-    const int fBeg = at<int>(arena, K2.offsets)[lo], fCnt = at<int>(arena, K2.offsets)[lo + 1] - fBeg;
-    const int kBeg = at<int>(arena, K1.offsets)[a], kCnt = at<int>(arena, K1.offsets)[a + 1] - kBeg;
+    const FtBowArenaSide K2 = job->K2;
+    if (K2.fv.n <= 0 || K2.fv.nNodes <= 0) return;  // nothing of an empty neighbour is dereferenced
+    const int lo = fv_find_node(at<unsigned>(arena, K2.fv.nodes), K2.fv.nNodes, at<unsigned>(arena, K1.fv.nodes)[a]);
+    if (lo < 0) return;
+    const int fBeg = at<int>(arena, K2.fv.offsets)[lo], fCnt = at<int>(arena, K2.fv.offsets)[lo + 1] - fBeg;
+    const int kBeg = at<int>(arena, K1.fv.offsets)[a], kCnt = at<int>(arena, K1.fv.offsets)[a + 1] - kBeg;
     if (fCnt <= 0 || kCnt <= 0) return;
-    const unsigned *feats1 = at<unsigned>(arena, K1.feats) + kBeg, *feats2 = at<unsigned>(arena, K2.feats) + fBeg;
+    const unsigned *feats1 = at<unsigned>(arena, K1.fv.feats) + kBeg, *feats2 = at<unsigned>(arena, K2.fv.feats) + fBeg;
     const uint8_t *has1 = at<uint8_t>(arena, K1.hasPoint), *has2 = at<uint8_t>(arena, K2.hasPoint);
     const uint8_t *desc1 = at<uint8_t>(arena, K1.desc), *desc2 = at<uint8_t>(arena, K2.desc);
     int *matches = (int *)(arena + job->matches);
@@ -85,12 +74,6 @@ __global__ __launch_bounds__(256) void k_bow_kf_match(FtBowKfCall T) {
         if (!__ballot(any1) || !__ballot(any2)) return;
     }
     constexpr unsigned NONE = (256u << 20) | 0xfffffu;  // bestDist = 256, no position
-    auto twoMin = [](unsigned &x0, unsigned &x1) {
-        const unsigned m0 = wave_min_u32(x0);
-        const unsigned m1 = wave_min_u32(x0 == m0 ? x1 : x0);
-        x0 = m0;
-        x1 = m1;
-    };
     // bestDist1 < TH_LOW, strictly (:947; not the <= of the KeyFrame, Frame overload at :426), and the ratio as one fp32 product
     auto accepted = [&](unsigned k0, unsigned k1) {
         const int bestDist1 = (int)(k0 >> 20), bestDist2 = (int)(k1 >> 20);
@@ -113,10 +96,6 @@ __global__ __launch_bounds__(256) void k_bow_kf_match(FtBowKfCall T) {
                 freeMask |= ((p < fCnt && eligible(K2.nLeft, K2.nUn, has2, fIdx[r])) ? 1u : 0u) << r;
             }
         }
-        auto bcast64 = [](unsigned long long v, int j) {
-            return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), j) << 32) |
-                   (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, j);
-        };
         for (int k0i = 0; k0i < kCnt; k0i += 64) {
             const int cnt = min(64, kCnt - k0i);
             const unsigned kIdx = feats1[k0i + min(lane, cnt - 1)];
@@ -127,7 +106,7 @@ __global__ __launch_bounds__(256) void k_bow_kf_match(FtBowKfCall T) {
                 const int j = __builtin_amdgcn_readfirstlane(jj);
                 if (!__builtin_amdgcn_readlane(el, j)) continue;
                 const int idx1 = __builtin_amdgcn_readlane((int)kIdx, j);
-                const unsigned long long b0 = bcast64(d0, j), b1 = bcast64(d1, j), b2 = bcast64(d2, j), b3 = bcast64(d3, j);
+                const unsigned long long b0 = wave_readlane_u64(d0, j), b1 = wave_readlane_u64(d1, j), b2 = wave_readlane_u64(d2, j), b3 = wave_readlane_u64(d3, j);
                 unsigned l0 = NONE, l1 = NONE;
 #pragma unroll
                 for (int r = 0; r < R; r++) {
@@ -137,7 +116,7 @@ __global__ __launch_bounds__(256) void k_bow_kf_match(FtBowKfCall T) {
                     l0 = min(l0, key);
                     l1 = min(l1, larger);
                 }
-                twoMin(l0, l1);
+                wave_two_min(l0, l1);
                 if (!accepted(l0, l1)) continue;
                 const int p = (int)(l0 & 0xfffffu);
                 if ((p & 63) == lane) {
@@ -170,7 +149,7 @@ __global__ __launch_bounds__(256) void k_bow_kf_match(FtBowKfCall T) {
             l0 = min(l0, key);
             l1 = min(l1, larger);
         }
-        twoMin(l0, l1);
+        wave_two_min(l0, l1);
         if (!accepted(l0, l1)) continue;
         const int p = (int)(l0 & 0xfffffu);
         if ((p & 63) == lane) {
@@ -182,52 +161,18 @@ __global__ __launch_bounds__(256) void k_bow_kf_match(FtBowKfCall T) {
 }
 
 __global__ __launch_bounds__(FT_BOWKF_FIN_T) void k_bow_kf_finish(FtBowKfCall T) {
-    __shared__ int hist[FT_HISTO_LENGTH];
-    __shared__ int keepBits, total;
     uint8_t *arena = T.arena;
-    const int tid = threadIdx.x, lane = tid & 63;
     const FtBowKfJob *job = at<FtBowKfJob>(arena, T.jobs) + blockIdx.x;
-    int *matches = (int *)(arena + job->matches);
     const float *angle1 = at<float>(arena, T.K1.angles), *angle2 = at<float>(arena, job->K2.angles);
-    const int n = T.K1.n;
-    if (tid < FT_HISTO_LENGTH) hist[tid] = 0;
-    if (tid == 0) total = 0;
-    __syncthreads();
-    if (T.checkOrientation) {
-        for (int i = tid; i < n; i += FT_BOWKF_FIN_T) {
-            const int m = matches[i];
-            if (m < 0) continue;
-            const int bin = init_bin(angle1[i], angle2[m]);  // vKeysUn1[idx1].angle - vKeysUn2[bestIdx2].angle (:956)
-            if (bin >= 0 && bin < FT_HISTO_LENGTH) atomicAdd(&hist[bin], 1);  // (the reference asserts)
-        }
-        __syncthreads();
-        if (tid == 0) keepBits = three_maxima_keep(hist);
-        __syncthreads();
-    }
-    const int keep = T.checkOrientation ? keepBits : -1;
-    int nm = 0;
-    for (int i = tid; i < n; i += FT_BOWKF_FIN_T) {
-        const int m = matches[i];
-        if (m < 0) continue;
-        if (T.checkOrientation) {
-            const int bin = init_bin(angle1[i], angle2[m]);
-            if (bin >= 0 && bin < FT_HISTO_LENGTH && !((keep >> bin) & 1)) {  // :991-1000
-                matches[i] = -1;
-                continue;
-            }
-        }
-        nm++;
-    }
-    nm = wave_sum_i32(nm);
-    if (lane == 0 && nm) atomicAdd(&total, nm);
-    __syncthreads();
-    if (tid == 0) ((int *)(arena + T.nMatches))[blockIdx.x] = total;
+    // vKeysUn1[idx1].angle - vKeysUn2[bestIdx2].angle (:956); the removal :983-1001
+    rot_filter_rows<FT_BOWKF_FIN_T>((int *)(arena + job->matches), T.K1.fv.n, T.checkOrientation, (int *)(arena + T.nMatches) + blockIdx.x,
+                                    [&](int i, int m) { return init_bin(angle1[i], angle2[m]); });
 }
 
 }  // namespace
 
 int ft_launch_bow_kf_match(hipStream_t st, const FtBowKfCall &T) {
-    const dim3 grid((unsigned)std::max((T.K1.nNodes + 3) / 4, 1), (unsigned)T.nNeighbours);
+    const dim3 grid((unsigned)std::max((T.K1.fv.nNodes + 3) / 4, 1), (unsigned)T.nNeighbours);
     hipLaunchKernelGGL(k_bow_kf_match, grid, dim3(256), 0, st, T);
     FT_HIP(hipGetLastError());
     return FT_OK;

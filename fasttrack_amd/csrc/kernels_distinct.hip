@@ -36,11 +36,6 @@ namespace {
 #define FT_DISTINCT_BLOCK_T 1024  // k_distinct_block: 64 rows of 16 lanes
 #define FT_DISTINCT_NOKEY 0xffffffffu
 
-template <class T>
-__device__ __forceinline__ const T *at(const uint8_t *arena, unsigned off) {
-    return (const T *)(arena + off);
-}
-
 __device__ __forceinline__ int hamming_u4(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1) {
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
            __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);

@@ -20,6 +20,7 @@
 #include <climits>
 
 #include "ft_search.h"
+#include "rot_filter_dev.h"
 #include "wave_ops.h"
 
 namespace {
@@ -190,14 +191,13 @@ __global__ __launch_bounds__(64 * FT_INIT_WPB) void k_init_candidates(FtInitSear
 #define FT_INIT_FREE 0xffffffffu
 __global__ __launch_bounds__(FT_INIT_RES_T) void k_init_resolve(FtInitSearch S) {
     extern __shared__ unsigned ini_lds[];
-    __shared__ int ini_hist[FT_HISTO_LENGTH], ini_keep, ini_nm;
+    __shared__ int ini_nm;
     const int tid = threadIdx.x, lane = tid & 63;
     const int n1 = __builtin_amdgcn_readfirstlane(S.counts[0]), n2 = __builtin_amdgcn_readfirstlane(S.counts[1]);
     unsigned *state = ini_lds;
     int *rowMatch = (int *)(ini_lds + S.cap2);
     for (int o = tid; o < n2; o += FT_INIT_RES_T) state[o] = FT_INIT_FREE;
     for (int r = tid; r < n1; r += FT_INIT_RES_T) rowMatch[r] = -1;
-    if (tid < FT_HISTO_LENGTH) ini_hist[tid] = 0;
     if (tid == 0) ini_nm = 0;
     // what the reference leaves for a keypoint that is no row or ends unmatched; the rows overwrite theirs at the end
     for (int i = tid; i < S.N1; i += FT_INIT_RES_T) {
@@ -282,39 +282,11 @@ __global__ __launch_bounds__(FT_INIT_RES_T) void k_init_resolve(FtInitSearch S) 
         const int ord = m >= 0 ? m : -2 - m;
         return init_bin(S.keys1[S.rows[r]].angle, F.keys[S.idxOfOrd[ord]].angle);
     };
-    if (S.checkOrientation) {
-        for (int r = tid; r < n1; r += FT_INIT_RES_T) {
-            const int m = rowMatch[r];
-            if (m == -1) continue;
-            const int bin = bin_of_row(r, m);
-            if (bin >= 0 && bin < FT_HISTO_LENGTH) atomicAdd(&ini_hist[bin], 1);  // (the reference asserts)
-        }
-        __syncthreads();
-        if (tid == 0) {  // ComputeThreeMaxima (src/ORBmatcher.cc:2210-2251)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int b = 0; b < FT_HISTO_LENGTH; b++) {
-                const int sz = ini_hist[b];
-                if (sz > max1) {
-                    max3 = max2; max2 = max1; max1 = sz;
-                    ind3 = ind2; ind2 = ind1; ind1 = b;
-                } else if (sz > max2) {
-                    max3 = max2; max2 = sz;
-                    ind3 = ind2; ind2 = b;
-                } else if (sz > max3) {
-                    max3 = sz; ind3 = b;
-                }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-            int keep = 0;
-            if (ind1 >= 0) keep |= 1 << ind1;
-            if (ind2 >= 0) keep |= 1 << ind2;
-            if (ind3 >= 0) keep |= 1 << ind3;
-            ini_keep = keep;
-        }
-        __syncthreads();
-    }
-    const int keep = S.checkOrientation ? ini_keep : -1;
+    // a row that was evicted (-2 - ord) stays in the bin it was filed under (:807 clears vnMatches12, not rotHist)
+    const int keep = rot_filter_keep<FT_INIT_RES_T>(n1, S.checkOrientation, [&](int r) {
+        const int m = rowMatch[r];
+        return m == -1 ? -1 : bin_of_row(r, m);
+    });
     int nm = 0;
     for (int r = tid; r < n1; r += FT_INIT_RES_T) {
         const int m = rowMatch[r];

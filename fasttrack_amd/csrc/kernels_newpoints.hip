@@ -25,11 +25,6 @@ namespace {
 
 #define FT_NEWPOINTS_T 256  // threads of a workgroup = slots of a chunk
 
-template <class T>
-__device__ __forceinline__ const T *at(const uint8_t *arena, unsigned off) {
-    return (const T *)(arena + off);
-}
-
 // pCamera->unprojectEig(kp.pt): Pinhole.cpp:61-64 / KannalaBrandt8.cpp:111-143
 template <int MODEL>
 __device__ __forceinline__ void unproject(const float *cam, float precision, float px, float py, float r[3]) {
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(FT_NEWPOINTS_T) void k_triang_points(FtTriangCall T
     __shared__ int waveCount[FT_NEWPOINTS_T / 64];
     uint8_t *arena = T.arena;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int k = blockIdx.y, n1 = T.K1.n;
+    const int k = blockIdx.y, n1 = T.K1.fv.n;
     const int base = (int)blockIdx.x * FT_NEWPOINTS_T;
     const FtTriangJob *job = at<FtTriangJob>(arena, T.jobs) + k;
     const FtNewPointJob *nj = at<FtNewPointJob>(arena, P.jobs) + k;
@@ -212,7 +207,7 @@ __global__ __launch_bounds__(FT_NEWPOINTS_T) void k_triang_points(FtTriangCall T
 }  // namespace
 
 int ft_launch_triang_points(hipStream_t st, const FtTriangCall &T, const FtNewPointCall &P) {
-    const dim3 grid((T.K1.n + FT_NEWPOINTS_T - 1) / FT_NEWPOINTS_T, T.nNeighbours);
+    const dim3 grid((T.K1.fv.n + FT_NEWPOINTS_T - 1) / FT_NEWPOINTS_T, T.nNeighbours);
     if (T.camModel == 0) hipLaunchKernelGGL(k_triang_points<0>, grid, dim3(FT_NEWPOINTS_T), 0, st, T, P);
     else hipLaunchKernelGGL(k_triang_points<1>, grid, dim3(FT_NEWPOINTS_T), 0, st, T, P);
     FT_HIP(hipGetLastError());

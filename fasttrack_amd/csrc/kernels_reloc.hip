@@ -19,6 +19,7 @@
 // Three launches per call, whatever the inputs hold.
 #include <algorithm>
 
+#include "rot_filter_dev.h"
 #include "search_dev.h"
 
 namespace {
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(64 * FT_RELOC_WPB) void k_reloc_candidates(FtRelocS
 #define FT_RELOC_RES_T 1024
 __global__ __launch_bounds__(FT_RELOC_RES_T) void k_reloc_resolve(FtRelocSearch S) {
     extern __shared__ unsigned rel_lds[];
-    __shared__ int rel_hist[FT_HISTO_LENGTH], rel_keep, rel_nm;
+    __shared__ int rel_nm;
     const int tid = threadIdx.x, lane = tid & 63;
     const FtDevFrame &F = S.F;
     const int nLeft = F.Nleft == -1 ? F.N : F.Nleft;
@@ -138,7 +139,6 @@ __global__ __launch_bounds__(FT_RELOC_RES_T) void k_reloc_resolve(FtRelocSearch 
     unsigned *taken = rel_lds;
     int *match = (int *)(rel_lds + nWords);
     for (int k = tid; k < nWords; k += FT_RELOC_RES_T) taken[k] = 0u;
-    if (tid < FT_HISTO_LENGTH) rel_hist[tid] = 0;
     if (tid == 0) rel_nm = 0;
     for (int k = tid; k < F.N; k += FT_RELOC_RES_T) S.assign[k] = -1;
     __threadfence();
@@ -211,24 +211,18 @@ __global__ __launch_bounds__(FT_RELOC_RES_T) void k_reloc_resolve(FtRelocSearch 
         }
     }
     __syncthreads();
-    if (S.checkOrientation) {
-        for (int i = tid; i < N; i += FT_RELOC_RES_T) {
-            const int m = match[i];
-            if (m < 0) continue;
-            const int bin = init_bin(S.angle[i], F.keys[m].angle);  // pKF->mvKeysUn[i].angle - CurrentFrame.mvKeysUn[bestIdx2].angle (:2171)
-            if (bin >= 0 && bin < FT_HISTO_LENGTH) atomicAdd(&rel_hist[bin], 1);  // (the reference asserts)
-        }
-        __syncthreads();
-        if (tid == 0) rel_keep = three_maxima_keep(rel_hist);
-        __syncthreads();
-    }
-    const int keep = S.checkOrientation ? rel_keep : -1;
+    // pKF->mvKeysUn[i].angle - CurrentFrame.mvKeysUn[bestIdx2].angle (:2171)
+    auto bin_of = [&](int i, int m) { return init_bin(S.angle[i], F.keys[m].angle); };
+    const int keep = rot_filter_keep<FT_RELOC_RES_T>(N, S.checkOrientation, [&](int i) {
+        const int m = match[i];
+        return m < 0 ? -1 : bin_of(i, m);
+    });
     int nm = 0;
     for (int i = tid; i < N; i += FT_RELOC_RES_T) {
         const int m = match[i];
         if (m < 0) continue;
         if (S.checkOrientation) {
-            const int bin = init_bin(S.angle[i], F.keys[m].angle);
+            const int bin = bin_of(i, m);
             if (bin >= 0 && bin < FT_HISTO_LENGTH && !((keep >> bin) & 1)) continue;  // removed (:2194-2204): the entry is NULL again
         }
         S.assign[m] = i;

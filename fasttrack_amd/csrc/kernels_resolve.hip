@@ -466,6 +466,7 @@ __global__ __launch_bounds__(256) void k_replay_batch(const FtBatchJob *__restri
     __syncthreads();
     // rotation bin of the write (point i -> keypoint kp): src/ORBmatcher.cc:1882-1890, the host replay's expression operation by operation
     auto bin_of = [&](int i, int kp) -> int {
+        // (init_bin written out: the call costs this kernel a 17th VGPR)
         const float cur = kp < nLk ? keys[kp].angle : keysR[kp - nLk].angle;
         float rot = __fsub_rn(lastAngle[i], cur);
         if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
@@ -489,28 +490,7 @@ __global__ __launch_bounds__(256) void k_replay_batch(const FtBatchJob *__restri
     if (!INLDS) __threadfence();
     __syncthreads();
     if (hist) {
-        if (tid == 0) {  // ComputeThreeMaxima (src/ORBmatcher.cc:2210-2251)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int b = 0; b < FT_HISTO_LENGTH; b++) {
-                const int sz = rp_hist[b];
-                if (sz > max1) {
-                    max3 = max2; max2 = max1; max1 = sz;
-                    ind3 = ind2; ind2 = ind1; ind1 = b;
-                } else if (sz > max2) {
-                    max3 = max2; max2 = sz;
-                    ind3 = ind2; ind2 = b;
-                } else if (sz > max3) {
-                    max3 = sz; ind3 = b;
-                }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-            int keep = 0;
-            if (ind1 >= 0) keep |= 1 << ind1;
-            if (ind2 >= 0) keep |= 1 << ind2;
-            if (ind3 >= 0) keep |= 1 << ind3;
-            rp_keep = keep;
-        }
+        if (tid == 0) rp_keep = three_maxima_keep(rp_hist);  // ComputeThreeMaxima (src/ORBmatcher.cc:2210-2251)
         __syncthreads();
         const int keep = rp_keep;
         for (int s = tid; s < 4 * M; s += 256) {

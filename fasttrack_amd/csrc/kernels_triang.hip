@@ -20,6 +20,7 @@
 #include "ft_internal.h"
 #include "ft_search.h"
 #include "kb8_triangulate.h"
+#include "rot_filter_dev.h"
 #include "wave_ops.h"
 
 namespace {
@@ -27,11 +28,6 @@ namespace {
 #define FT_TRIANG_T 256                    // threads of a k_triang_match workgroup
 #define FT_TRIANG_ROWS (FT_TRIANG_T / 16)  // features of keyframe 1 per workgroup
 #define FT_TRIANG_FIN_T 256
-
-template <class T>
-__device__ __forceinline__ const T *at(const uint8_t *arena, unsigned off) {
-    return (const T *)(arena + off);
-}
 
 // Pinhole::epipolarConstrain (src/CameraModels/Pinhole.cpp:107-129) behind the line [a b c] = x1' F12 of the feature
 __device__ __forceinline__ bool pinhole_constrain(float a, float b, float c, float x2, float y2, float unc) {
@@ -52,7 +48,7 @@ __global__ __launch_bounds__(FT_TRIANG_T) void k_triang_match(FtTriangCall T) {
     const FtTriangSide &K2 = job->K2;
     constexpr unsigned NONE = 0xffffffffu;
     unsigned best = NONE;
-    const bool live = idx1 < K1.n;
+    const bool live = idx1 < K1.fv.n;
     // every lane of a row takes the same way through the tests of the feature: the row stays whole for its reduction
     int a1 = live ? at<int>(arena, T.nodeOf)[idx1] : -1;
     if (a1 >= 0 && at<uint8_t>(arena, K1.hasPoint)[idx1]) a1 = -1;  // pMP1 (:1073)
@@ -63,16 +59,9 @@ __global__ __launch_bounds__(FT_TRIANG_T) void k_triang_match(FtTriangCall T) {
     }
     int fBeg = 0, fCnt = 0;
     if (a1 >= 0) {
-        const unsigned node = at<unsigned>(arena, K1.nodes)[a1];
-        const unsigned *nodes2 = at<unsigned>(arena, K2.nodes);
-        int lo = 0, hi = K2.nNodes;  // lower_bound
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (nodes2[mid] < node) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo < K2.nNodes && nodes2[lo] == node) {
-            const int *offs2 = at<int>(arena, K2.offsets);
+        const int lo = fv_find_node(at<unsigned>(arena, K2.fv.nodes), K2.fv.nNodes, at<unsigned>(arena, K1.fv.nodes)[a1]);
+        if (lo >= 0) {
+            const int *offs2 = at<int>(arena, K2.fv.offsets);
             fBeg = offs2[lo];
             fCnt = offs2[lo + 1] - fBeg;
         }
@@ -93,7 +82,7 @@ __global__ __launch_bounds__(FT_TRIANG_T) void k_triang_match(FtTriangCall T) {
             lb = __fadd_rn(__fadd_rn(__fmul_rn(kp1.x, F[1]), __fmul_rn(kp1.y, F[4])), F[7]);
             lc = __fadd_rn(__fadd_rn(__fmul_rn(kp1.x, F[2]), __fmul_rn(kp1.y, F[5])), F[8]);
         }
-        const unsigned *feats2 = at<unsigned>(arena, K2.feats) + fBeg;
+        const unsigned *feats2 = at<unsigned>(arena, K2.fv.feats) + fBeg;
         const uint8_t *has2 = at<uint8_t>(arena, K2.hasPoint);
         const ft_keypoint *keys2 = at<ft_keypoint>(arena, K2.keys);
         for (int p = sub; p < fCnt; p += 16) {
@@ -133,7 +122,7 @@ __global__ __launch_bounds__(FT_TRIANG_T) void k_triang_match(FtTriangCall T) {
         int m = -1, bd = FT_TH_LOW;
         if (best != NONE) {
             bd = (int)(best >> 20);
-            m = (int)at<unsigned>(arena, K2.feats)[fBeg + (int)(0xfffffu - (best & 0xfffffu))];
+            m = (int)at<unsigned>(arena, K2.fv.feats)[fBeg + (int)(0xfffffu - (best & 0xfffffu))];
         }
         ((int *)(arena + job->matches))[idx1] = m;
         ((int *)(arena + job->bestDist))[idx1] = bd;
@@ -141,52 +130,18 @@ __global__ __launch_bounds__(FT_TRIANG_T) void k_triang_match(FtTriangCall T) {
 }
 
 __global__ __launch_bounds__(FT_TRIANG_FIN_T) void k_triang_finish(FtTriangCall T) {
-    __shared__ int hist[FT_HISTO_LENGTH];
-    __shared__ int keepBits, total;
     uint8_t *arena = T.arena;
-    const int tid = threadIdx.x, lane = tid & 63;
     const FtTriangJob *job = at<FtTriangJob>(arena, T.jobs) + blockIdx.x;
-    int *matches = (int *)(arena + job->matches);
     const ft_keypoint *keys1 = at<ft_keypoint>(arena, T.K1.keys), *keys2 = at<ft_keypoint>(arena, job->K2.keys);
-    const int n = T.K1.n;
-    if (tid < FT_HISTO_LENGTH) hist[tid] = 0;
-    if (tid == 0) total = 0;
-    __syncthreads();
-    if (T.checkOrientation) {
-        for (int i = tid; i < n; i += FT_TRIANG_FIN_T) {
-            const int m = matches[i];
-            if (m < 0) continue;
-            const int bin = init_bin(keys1[i].angle, keys2[m].angle);  // kp1.angle - kp2.angle (:1188)
-            if (bin >= 0 && bin < FT_HISTO_LENGTH) atomicAdd(&hist[bin], 1);  // (the reference asserts)
-        }
-        __syncthreads();
-        if (tid == 0) keepBits = three_maxima_keep(hist);
-        __syncthreads();
-    }
-    const int keep = T.checkOrientation ? keepBits : -1;
-    int nm = 0;
-    for (int i = tid; i < n; i += FT_TRIANG_FIN_T) {
-        const int m = matches[i];
-        if (m < 0) continue;
-        if (T.checkOrientation) {
-            const int bin = init_bin(keys1[i].angle, keys2[m].angle);
-            if (bin >= 0 && bin < FT_HISTO_LENGTH && !((keep >> bin) & 1)) {  // :1221-1230
-                matches[i] = -1;
-                continue;
-            }
-        }
-        nm++;
-    }
-    nm = wave_sum_i32(nm);
-    if (lane == 0 && nm) atomicAdd(&total, nm);
-    __syncthreads();
-    if (tid == 0) ((int *)(arena + T.nMatches))[blockIdx.x] = total;
+    // kp1.angle - kp2.angle (:1188); the removal :1221-1230
+    rot_filter_rows<FT_TRIANG_FIN_T>((int *)(arena + job->matches), T.K1.fv.n, T.checkOrientation, (int *)(arena + T.nMatches) + blockIdx.x,
+                                     [&](int i, int m) { return init_bin(keys1[i].angle, keys2[m].angle); });
 }
 
 }  // namespace
 
 int ft_launch_triang_match(hipStream_t st, const FtTriangCall &T) {
-    const dim3 grid((T.K1.n + FT_TRIANG_ROWS - 1) / FT_TRIANG_ROWS, T.nNeighbours);
+    const dim3 grid((T.K1.fv.n + FT_TRIANG_ROWS - 1) / FT_TRIANG_ROWS, T.nNeighbours);
     if (T.camModel == 0) hipLaunchKernelGGL(k_triang_match<0>, grid, dim3(FT_TRIANG_T), 0, st, T);
     else hipLaunchKernelGGL(k_triang_match<1>, grid, dim3(FT_TRIANG_T), 0, st, T);
     FT_HIP(hipGetLastError());

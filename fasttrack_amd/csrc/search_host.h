@@ -1,6 +1,6 @@
 // Host side of the projection searches, shared by the translation units of the entry-point families (search_view.cpp,
 // tracked_frame.cpp, init_search.cpp, reloc_search.cpp, triang_search.cpp and newpoints.cpp (through triang_host.h), fuse_search.cpp, sim3_search.cpp, tracked_batch.cpp; bow.cpp, bow_kf_search.cpp,
-// distinct_desc.cpp and fisheye_match.cpp for the call skeleton at the end: Arena, CallScope): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
+// distinct_desc.cpp and fisheye_match.cpp for the call skeleton at the end: CallScope, over the Arena of fv_host.h): replaces launchSearchLocalPointsKernel / launchPoseEstimationKernel
 // (reference include/Kernels/KernelController.h:40-46) together with the acceptance loops the reference keeps in the caller
 // (src/ORBmatcher.cc:241-308, 2013-2081).  Windowing, level/box tests and every Hamming distance run on the device
 // (kernels_search*.hip, kernels_resolve.hip, kernels_frame.hip); the host only marshals arrays, drives the fixed-point passes and
@@ -14,16 +14,19 @@
 
 #include "ft_host.h"
 #include "ft_search.h"
+#include "fv_host.h"
 #include "rot_hist.h"
 
-struct Arena {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t o = off;
-        off = (off + bytes + 63) & ~(size_t)63;
-        return o;
-    }
+// One ft_bow_side in the arena of a SearchByBoW call (bow.cpp, beside checkBowSide): the FeatureVector, then what the call stages of
+// the side - has: its has_point, desc: its descriptors (not those of a frame that are resident on the device), angles: its
+// keypoint angles (check_orientation).  The FeatureVector comes first, so offset 0 = "not in the arena".
+struct BowSideLayout {
+    FvLayout fv;
+    size_t desc, hasPoint, angles;
 };
+BowSideLayout layoutBowSide(Arena &a, const ft_bow_side *s, bool has, bool desc, bool angles);
+// fills the arena's pinned mirror; the record says nLeft = -1, nUn = n (a side without a second camera)
+FtBowArenaSide stageBowSide(const ft_bow_side *s, const uint8_t *has, const BowSideLayout &L, uint8_t *pin);
 
 struct FrameLayout {
     size_t keys, keysR, desc, uright, holder, l2r, r2l;

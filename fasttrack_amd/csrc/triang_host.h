@@ -9,11 +9,11 @@
 #include "search_host.h"
 
 struct TriangSideLayout {
-    size_t keys, desc, nodes, offsets, feats, hasPoint, uright, sf, sigma2;
-    int total;  // FeatureVector entries
+    size_t keys, desc, hasPoint, uright, sf, sigma2;
+    FvLayout fv;
 };
 
-inline int checkTriangSide(const ft_triang_keyframe *s, const std::string &w, std::vector<uint8_t> &seen, bool search = true) {
+inline int checkTriangSide(const ft_triang_keyframe *s, const std::string &w, bool search = true) {
     FT_REQUIRE(s->n >= 0 && s->n < (1 << 20) && (!search || s->n_nodes >= 0), w + "count out of range");
     FT_REQUIRE(s->n_left >= -1 && s->n_left <= s->n, w + "n_left out of range");
     FT_REQUIRE(s->cam_model == 0 || s->cam_model == 1, w + "unknown camera model");
@@ -21,32 +21,18 @@ inline int checkTriangSide(const ft_triang_keyframe *s, const std::string &w, st
     FT_REQUIRE(s->scale_factors && s->level_sigma2 && s->nlevels >= 1 && s->nlevels <= FT_MAX_LEVELS, w + "scale factors / level sigmas missing");
     FT_REQUIRE(s->n == 0 || (s->keys && (!search || (s->descriptors && s->has_point))), w + "keypoints, descriptors or has_point are null");
     for (int i = 0; i < s->n; i++) FT_REQUIRE(s->keys[i].octave >= 0 && s->keys[i].octave < s->nlevels, w + "keypoint octave outside [0, nlevels)");
-    if (!search || s->n_nodes == 0) return FT_OK;
-    FT_REQUIRE(s->fv_nodes && s->fv_offsets, w + "null feature vector");
-    FT_REQUIRE(s->fv_offsets[0] == 0, w + "fv_offsets[0] != 0");
-    for (int j = 0; j < s->n_nodes; j++) {
-        FT_REQUIRE(s->fv_offsets[j + 1] >= s->fv_offsets[j], w + "fv_offsets not ascending");
-        FT_REQUIRE(j == 0 || s->fv_nodes[j] > s->fv_nodes[j - 1], w + "fv_nodes not strictly ascending");
-    }
-    const int total = s->fv_offsets[s->n_nodes];
-    FT_REQUIRE(total <= s->n, w + "more feature-vector entries than features");
-    FT_REQUIRE(total == 0 || s->fv_features, w + "null fv_features");
-    seen.assign((size_t)s->n, 0);
-    for (int e = 0; e < total; e++) {
-        FT_REQUIRE(s->fv_features[e] < (unsigned)s->n, w + "feature index out of range");
-        FT_REQUIRE(!seen[s->fv_features[e]], w + "a feature is listed twice");  // a FeatureVector holds a feature under one node
-        seen[s->fv_features[e]] = 1;
-    }
+    if (!search) return FT_OK;
+    const char *what = checkFv(fvOf(*s), true);  // a FeatureVector holds a feature under one node
+    FT_REQUIRE(!what, w + what);
     return FT_OK;
 }
 
 // keyframe 1 and the neighbours of a call: every side, and that they agree in two_cameras and in the camera model
 inline int checkTriangCall(const std::string &fn, const ft_triang_keyframe *kf1, int n_neighbours, const ft_triang_keyframe *kf2, bool search) {
-    std::vector<uint8_t> seen;
-    int rc = checkTriangSide(kf1, fn + ": keyframe 1: ", seen, search);
+    int rc = checkTriangSide(kf1, fn + ": keyframe 1: ", search);
     if (rc != FT_OK) return rc;
     for (int k = 0; k < n_neighbours; k++) {
-        rc = checkTriangSide(kf2 + k, fn + ": neighbour " + std::to_string(k) + ": ", seen, search);
+        rc = checkTriangSide(kf2 + k, fn + ": neighbour " + std::to_string(k) + ": ", search);
         if (rc != FT_OK) return rc;
         // the reference reads an uninitialised R12 when only one of the two keyframes has a second camera (:1027-1039, :1135)
         FT_REQUIRE(!kf2[k].two_cameras == !kf1->two_cameras && kf2[k].cam_model == kf1->cam_model,
@@ -58,14 +44,11 @@ inline int checkTriangCall(const std::string &fn, const ft_triang_keyframe *kf1,
 inline TriangSideLayout layoutTriangSide(Arena &a, const ft_triang_keyframe *s, bool search = true) {
     TriangSideLayout L;
     memset(&L, 0, sizeof L);
-    const size_t n = (size_t)std::max(s->n, 1), nn = search ? (size_t)s->n_nodes : 0;
-    L.total = nn ? s->fv_offsets[s->n_nodes] : 0;
+    const size_t n = (size_t)std::max(s->n, 1);
     L.keys = a.take(sizeof(ft_keypoint) * n);
     if (search) {
         L.desc = a.take(32 * n);
-        L.nodes = a.take(4 * std::max(nn, (size_t)1));
-        L.offsets = a.take(4 * (nn + 1));
-        L.feats = a.take(4 * (size_t)std::max(L.total, 1));
+        L.fv = layoutFv(a, fvOf(*s));
         L.hasPoint = a.take(n);
     }
     L.uright = s->uright ? a.take(4 * n) : 0;
@@ -75,7 +58,7 @@ inline TriangSideLayout layoutTriangSide(Arena &a, const ft_triang_keyframe *s, 
 }
 
 inline FtTriangSide stageTriangSide(const ft_triang_keyframe *s, const TriangSideLayout &L, uint8_t *pin, bool search = true) {
-    const size_t n = (size_t)s->n, nn = search ? (size_t)s->n_nodes : 0;
+    const size_t n = (size_t)s->n;
     if (n) {
         memcpy(pin + L.keys, s->keys, sizeof(ft_keypoint) * n);
         if (search) {
@@ -84,24 +67,13 @@ inline FtTriangSide stageTriangSide(const ft_triang_keyframe *s, const TriangSid
         }
         if (s->uright) memcpy(pin + L.uright, s->uright, 4 * n);
     }
-    if (nn) {
-        memcpy(pin + L.nodes, s->fv_nodes, 4 * nn);
-        memcpy(pin + L.offsets, s->fv_offsets, 4 * (nn + 1));
-        if (L.total) memcpy(pin + L.feats, s->fv_features, 4 * (size_t)L.total);
-    } else if (search) {
-        memset(pin + L.offsets, 0, 4);
-    }
     memcpy(pin + L.sf, s->scale_factors, 4 * (size_t)s->nlevels);
     memcpy(pin + L.sigma2, s->level_sigma2, 4 * (size_t)s->nlevels);
     FtTriangSide D;
-    D.n = s->n;
+    D.fv = search ? stageFv(fvOf(*s), L.fv, pin) : FtFv{s->n, 0, 0, 0, 0};
     D.nLeft = s->n_left;
-    D.nNodes = (int)nn;
     D.keys = (unsigned)L.keys;
     D.desc = (unsigned)L.desc;
-    D.nodes = (unsigned)L.nodes;
-    D.offsets = (unsigned)L.offsets;
-    D.feats = (unsigned)L.feats;
     D.hasPoint = (unsigned)L.hasPoint;
     D.uright = s->uright ? (unsigned)L.uright : FT_TRIANG_NONE;
     D.sf = (unsigned)L.sf;

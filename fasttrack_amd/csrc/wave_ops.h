@@ -50,6 +50,19 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
                min((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
 }
 
+// the two smallest of the 2 x 64 keys of a wave whose lanes each hold their own two smallest (x0 <= x1), wave-uniform in x0 <= x1
+__device__ __forceinline__ void wave_two_min(unsigned &x0, unsigned &x1) {
+    const unsigned m0 = wave_min_u32(x0);
+    const unsigned m1 = wave_min_u32(x0 == m0 ? x1 : x0);
+    x0 = m0;
+    x1 = m1;
+}
+// lane j's 64-bit value (j wave-uniform) as two v_readlane, wave-uniform
+__device__ __forceinline__ unsigned long long wave_readlane_u64(unsigned long long v, int j) {
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), j) << 32) |
+           (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, j);
+}
+
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
 #define FT_MIN64_STEP(ctrl)                                                                                   \
     {                                                                                                         \

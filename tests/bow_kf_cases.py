@@ -165,6 +165,60 @@ def _hand_kf(desc, lists, angles=None, has_point=None, n_left=-1, n_un=None):
                     np.ones(n, np.uint8) if has_point is None else has_point, n_left, n_un)
 
 
+def angles_decide(ang1, ang2, seed=7):
+    """Two sides whose angles alone decide: feature i of side 1 (angle ang1[i]) has a vocabulary node of its own, and so has feature
+    i of side 2 (angle ang2[i]), a copy of it - one candidate at distance 0 each, so every feature i < len(ang2) matches feature i
+    before the rotation filter and the others nothing.  -> (descriptors [n1, 32], lists of side 1, lists of side 2); side 2 takes
+    the first len(ang2) descriptors"""
+    n1, n2 = len(ang1), len(ang2)
+    assert n2 <= n1
+    d = np.random.default_rng(seed).integers(0, 256, (n1, 32), dtype=np.uint8)
+    return d, {10 + i: [i] for i in range(n1)}, {10 + i: [i] for i in range(n2)}
+
+
+def rotation_table():
+    """ROTATION_CASES of tests/test_search_geometry_cpu.py - bin -> count with the bins that survive ComputeThreeMaxima listed by
+    hand - without `doubles` (two writes to one keypoint: specific to the last-frame search) -> [(name, rot [n] float32 degrees,
+    kept [n] bool, number kept)]: one match per count of a bin with rotation 30 * bin, in the order of the spec.  The bin of a
+    rotation is written as in rotation_expectation there; no library code takes part."""
+    from tests.test_search_geometry_cpu import ROTATION_CASES
+    out = []
+    for name, (spec, _, kept_bins, n_kept) in ROTATION_CASES.items():
+        if name == "doubles":
+            continue
+        rot = np.array([30.0 * b for b, cnt in spec.items() for _ in range(cnt)], f32)
+        bins = np.round(np.mod(rot.astype(np.float64), 360.0) / 30.0).astype(int)
+        kept = np.isin(bins, sorted(kept_bins))
+        assert len(rot) <= 200 and int(kept.sum()) == n_kept, name
+        out.append((name, rot, kept, n_kept))
+    return out
+
+
+def rotation_cases():
+    """the table above as cases of hand_built()'s form: one per histogram, check_orientation on, and `rotation_all_in_one_call`
+    (on and off) with every histogram as a neighbour of the SAME keyframe 1 - angle 0 everywhere, so a match's rotation is minus
+    the neighbour's angle.  A neighbour has as many features as its histogram has matches."""
+    table = rotation_table()
+    out = []
+
+    def case(name, n1, rots, ori):
+        d, lists1, _ = angles_decide(np.zeros(n1), [])
+        nbs, want = [], np.full((len(rots), n1), -1, np.int32)
+        for k, (rot, kept) in enumerate(rots):
+            nbs.append(_hand_kf(d[:len(rot)], {10 + i: [i] for i in range(len(rot))}, angles=-rot))
+            hit = np.nonzero(kept | (not ori))[0]
+            want[k, hit] = hit
+        out.append(dict(name=name, kf1=_hand_kf(d, lists1, angles=np.zeros(n1)), neighbours=nbs, nn_ratio=0.9, check_orientation=ori,
+                        matches12=want, n=(want >= 0).sum(axis=1).astype(np.int32)))
+
+    for name, rot, kept, _ in table:
+        case("rotation_" + name, max(len(rot), 1), [(rot, kept)], True)
+    n1 = max(len(rot) for _, rot, _, _ in table)
+    for ori in (True, False):
+        case("rotation_all_in_one_call" + ("" if ori else "_filter_off"), n1, [(rot, kept) for _, rot, kept, _ in table], ori)
+    return out
+
+
 def hand_built():
     """-> list of dict(name, kf1, neighbours, nn_ratio, check_orientation, matches12 [J, n1], n [J]): the expected outputs are
     written out from the reference text, not computed"""
@@ -226,9 +280,7 @@ def hand_built():
         ang2 = [b for cnt, _, b, _ in groups for _ in range(cnt)]
         kept = [k for cnt, _, _, k in groups for _ in range(cnt)]
         n = len(ang1)
-        rng = np.random.default_rng(7)
-        d = rng.integers(0, 256, (n, 32), dtype=np.uint8)
-        lists = {10 + i: [i] for i in range(n)}
+        d, lists, _ = angles_decide(ang1, ang2)
         want = [i if (kept[i] or not ori) else -1 for i in range(n)]
         case(name, _hand_kf(d, lists, angles=ang1), [_hand_kf(d, lists, angles=ang2)], 0.9, ori, [want], [sum(w >= 0 for w in want)])
 

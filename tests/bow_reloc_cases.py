@@ -161,6 +161,33 @@ def hand_built():
     return out
 
 
+def rotation_cases():
+    """the directed histograms of the rotation filter (bow_kf_cases.rotation_table) as cases of hand_built()'s form: one per
+    histogram, and `rotation_all_in_one_call` (filter on and off) with every histogram as a candidate of the SAME frame.  The bin is
+    the keyframe's angle minus the frame's (:491) while the row is the frame's: the frame's angles are 0 and a candidate's are
+    its matches' rotations - the other way round than for the keyframe matcher."""
+    table = bk.rotation_table()
+    out = []
+
+    def case(name, n_f, rots, ori):
+        d, lists, _ = bk.angles_decide(np.zeros(n_f), [])
+        cands, want = [], np.full((len(rots), n_f), -1, np.int32)
+        for k, (rot, kept) in enumerate(rots):
+            n = len(rot)
+            cands.append(side(bk._fv({10 + i: [i] for i in range(n)}), d[:n], rot, np.ones(n, np.uint8)))
+            hit = np.nonzero(kept | (not ori))[0]
+            want[k, hit] = hit
+        out.append(dict(name=name, frame=side(bk._fv(lists), d, np.zeros(n_f)), nleft=-1, candidates=cands, nn_ratio=0.75,
+                        check_orientation=ori, matches=want, n=(want >= 0).sum(axis=1).astype(np.int32)))
+
+    for name, rot, kept, _ in table:
+        case("rotation_" + name, max(len(rot), 1), [(rot, kept)], True)
+    n_f = max(len(rot) for _, rot, _, _ in table)
+    for ori in (True, False):
+        case("rotation_all_in_one_call" + ("" if ori else "_filter_off"), n_f, [(rot, kept) for _, rot, kept, _ in table], ori)
+    return out
+
+
 def to_device(orb, S, candidates=None):
     """-> (BowSide of the frame, [BowCandidate])"""
     f = S["frame"]

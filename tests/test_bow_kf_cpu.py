@@ -44,7 +44,7 @@ def test_the_strict_threshold_is_visible():
         assert _pair_runs(a, o)[3]["stats"]["dist_50"] > 0
 
 
-@pytest.mark.parametrize("case", bc.hand_built(), ids=lambda c: c["name"])
+@pytest.mark.parametrize("case", bc.hand_built() + bc.rotation_cases(), ids=lambda c: c["name"])
 def test_hand_built_cases(case):
     for k, nb in enumerate(case["neighbours"]):
         r = br.search_by_bow_keyframes(case["kf1"], nb, case["nn_ratio"], case["check_orientation"])

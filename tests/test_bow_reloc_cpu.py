@@ -65,8 +65,9 @@ def test_node_size_cases_have_exactly_their_sizes():
             assert n >= 6, (k_kf, k_f, two, n)
 
 
-@pytest.mark.parametrize("case", rc.hand_built(), ids=lambda c: c["name"])
+@pytest.mark.parametrize("case", rc.hand_built() + rc.rotation_cases(), ids=lambda c: c["name"])
 def test_hand_built_cases(case):
     r = rc.oracle(case, case["nn_ratio"], case["check_orientation"])
-    assert len(r) == 1
-    assert np.array_equal(r[0]["matches"], case["matches"][0]) and r[0]["n"] == case["n"][0], (r[0]["matches"], r[0]["n"])
+    assert len(r) == len(case["candidates"]) >= 1
+    for k in range(len(r)):
+        assert np.array_equal(r[k]["matches"], case["matches"][k]) and r[k]["n"] == case["n"][k], (k, r[k]["matches"], r[k]["n"])

@@ -135,6 +135,22 @@ def test_rot_hist_matches_compute_three_maxima(tmp_path):
     assert out.returncode == 0 and "histograms 6000 mismatches 0" in out.stdout, out.stdout + out.stderr
 
 
+def test_fv_host_checks_lays_out_and_stages(tmp_path, capsys):
+    """fv_host.h, the host's one FeatureVector helper (ft_search_by_bow, its two batched forms, the triangulation calls): every
+    rejection by its text, layout and staged bytes against values written out by hand, guard bytes around them.  A stand-alone
+    program, built with AddressSanitizer and UBSan where they link and without them otherwise."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "tfv")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", os.path.join(root, "tests", "cpp", "test_fv_host.cpp"), "-o", exe]
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    if subprocess.run(cmd + san, capture_output=True).returncode != 0:
+        with capsys.disabled():
+            print("test_fv_host.cpp: the sanitizers do not link here, built without them")
+        subprocess.check_call(cmd)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and " failed 0" in out.stdout, out.stdout + out.stderr
+
+
 @pytest.mark.parametrize("mode", ["1", "2", "3"])
 def test_path_code_octree_equals_oracle(mode):
     """The path-code formulations the device kernel is built from (octree_paths.h; 1 = node-list replay over

@@ -97,7 +97,7 @@ def test_neighbour_counts_and_batching(ctx):
         assert np.array_equal(g1["matches12"][0], g5["matches12"][k])
 
 
-@pytest.mark.parametrize("case", bc.hand_built(), ids=lambda c: c["name"])
+@pytest.mark.parametrize("case", bc.hand_built() + bc.rotation_cases(), ids=lambda c: c["name"])
 def test_hand_built_cases(ctx, case):
     g = run(ctx, case["kf1"], case["neighbours"], case["nn_ratio"], case["check_orientation"])
     assert np.array_equal(g["matches12"], case["matches12"]), g["matches12"]

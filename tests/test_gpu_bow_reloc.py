@@ -109,11 +109,20 @@ def test_seventy_candidates_in_one_call(ctx):
     check(70, run(ctx, S), want)
 
 
-@pytest.mark.parametrize("case", rc.hand_built(), ids=lambda c: c["name"])
+@pytest.mark.parametrize("case", rc.hand_built() + rc.rotation_cases(), ids=lambda c: c["name"])
 def test_hand_built_cases(ctx, case):
     g = run(ctx, case, case["nn_ratio"], case["check_orientation"])
     assert np.array_equal(g["matches"], case["matches"]), g["matches"]
     assert np.array_equal(g["n"], case["n"]), g["n"]
+
+
+@pytest.mark.parametrize("case", rc.rotation_cases(), ids=lambda c: c["name"])
+def test_rotation_cases_through_search_by_bow(ctx, case):
+    """the same frame / candidate pairs through ft_search_by_bow, whose filter is the host's (rot_hist.h): the hand-listed rows pin
+    the host twin and the device twin against each other"""
+    for k, c in enumerate(case["candidates"]):
+        s = single(ctx, case, c, case["nn_ratio"], case["check_orientation"])
+        assert np.array_equal(s["matches"], case["matches"][k]) and s["n"] == case["n"][k], (k, s["matches"], s["n"])
 
 
 @pytest.mark.parametrize("i", [1, 3])

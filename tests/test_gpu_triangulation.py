@@ -103,6 +103,14 @@ def test_hand_built_cases(ctx, case):
     assert int(g["n"][0]) == case["n"] and np.array_equal(g["best_dist"][0], case["best_dist"]), (g["n"], g["best_dist"][0])
 
 
+@pytest.mark.parametrize("case", tc.rotation_cases(), ids=lambda c: c["name"])
+def test_rotation_cases(ctx, case):
+    """the directed histograms the matchers share, one per call and all as the neighbours of one call"""
+    g = run(ctx, case, case["flags"])
+    assert np.array_equal(g["matches12"], case["matches12"]), g["matches12"]
+    assert np.array_equal(g["n"], case["n"]) and np.array_equal(g["best_dist"], case["best_dist"]), (g["n"], g["best_dist"])
+
+
 def test_the_four_pairings(ctx):
     kf1, kf2, P = tc.four_pairings()
     S = dict(kf1=kf1, neighbours=[kf2], pairs=[P])

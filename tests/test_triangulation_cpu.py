@@ -92,6 +92,16 @@ def test_hand_built_cases(case):
         assert r["n"] == case["n"] and np.array_equal(r["best_dist"], case["best_dist"]), (fn.__name__, r["n"], r["best_dist"])
 
 
+@pytest.mark.parametrize("case", tc.rotation_cases(), ids=lambda c: c["name"])
+def test_rotation_cases(case):
+    """the shared directed histograms: the restatement gives the hand-listed rows"""
+    for k, (kf2, pair) in enumerate(zip(case["neighbours"], case["pairs"])):
+        for fn in (tr.search_for_triangulation, order_free):
+            r = fn(case["kf1"], kf2, pair, *case["flags"])
+            assert np.array_equal(r["matches12"], case["matches12"][k]), (fn.__name__, k, r["matches12"])
+            assert r["n"] == case["n"][k] and np.array_equal(r["best_dist"], case["best_dist"][k]), (fn.__name__, k, r["n"])
+
+
 def test_the_four_pairings_reach_the_oracle_with_their_own_cameras_and_pose():
     kf1, kf2, P = tc.four_pairings()
     calls = []

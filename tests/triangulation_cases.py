@@ -322,6 +322,38 @@ def hand_built():
     return out
 
 
+def rotation_cases():
+    """the directed histograms of the rotation filter (bow_kf_cases.rotation_table) -> list of dict(name, kf1, neighbours, pairs,
+    flags, matches12 [J, n1], n [J], best_dist [J, n1]): one per histogram, and `rotation_all_in_one_call` (filter on and off) with
+    every histogram as a neighbour of the SAME keyframe 1.  All features share one node; the descriptors are unrelated (pairwise
+    distances far above TH_LOW), a neighbour's are copies of keyframe 1's first ones, so feature i matches its copy at distance 0
+    (bCoarse: no constraint) and the features beyond a neighbour's nothing.  Keyframe 1's angles are 0, a neighbour's minus its
+    matches' rotations (kp1.angle - kp2.angle, :1188)."""
+    from tests import bow_kf_cases as bk
+    table = bk.rotation_table()
+    out = []
+
+    def case(name, n1, rots, ori):
+        d = bk.angles_decide(np.zeros(n1), [])[0]
+        xy = [[20 + 10 * i, 30 + 8 * i] for i in range(n1)]
+        nbs, want, best = [], np.full((len(rots), n1), -1, np.int32), np.full((len(rots), n1), 50, np.int32)
+        for k, (rot, kept) in enumerate(rots):
+            n = len(rot)
+            nbs.append(_hand_kf(xy[:n], d[:n], angle=-rot))
+            hit = np.nonzero(kept | (not ori))[0]
+            want[k, hit] = hit
+            best[k, :n] = 0  # bestDist of a match the histogram removes stays
+        out.append(dict(name=name, kf1=_hand_kf(xy, d), neighbours=nbs, pairs=[_hand_pair() for _ in rots], flags=(False, True, ori),
+                        matches12=want, n=(want >= 0).sum(axis=1).astype(np.int32), best_dist=best))
+
+    for name, rot, kept, _ in table:
+        case("rotation_" + name, max(len(rot), 1), [(rot, kept)], True)
+    n1 = max(len(rot) for _, rot, _, _ in table)
+    for ori in (True, False):
+        case("rotation_all_in_one_call" + ("" if ori else "_filter_off"), n1, [(rot, kept) for _, rot, kept, _ in table], ori)
+    return out
+
+
 def four_pairings():
     """two-camera keyframes with one left and one right feature each, all four with the same descriptor in one node, and four
     distinguishable poses -> (kf1, kf2, pair)"""
