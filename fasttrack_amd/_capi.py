@@ -19,6 +19,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "fasttrack_amd.h")
 FT_OK, FT_ERR_INVALID, FT_ERR_NO_DEVICE, FT_ERR_HIP, FT_ERR_CAPACITY, FT_ERR_EMPTY = 0, -1, -2, -3, -4, -5
 DISTINCT_MAX_OBSERVATIONS = 1024  # FT_DISTINCT_MAX_OBSERVATIONS: the longest list of ft_distinctive_descriptors
 POSE_OPT_MAX_EDGES = 2000  # FT_POSE_OPT_MAX_EDGES: the most correspondences of a frame of ft_pose_optimization
+SIM3_MAX_ITERATIONS = 1024  # FT_SIM3_MAX_ITERATIONS: the most iterations a problem of ft_sim3_solver may ask for
+SIM3_RAND_MAX = 2147483647  # FT_SIM3_RAND_MAX: the largest draw of ft_sim3_problem.rand_draws (glibc's RAND_MAX)
 KFDB_MAX_QUERY_WORDS = 4096  # FT_KFDB_MAX_QUERY_WORDS: the longest query of ft_kfdb_score
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
@@ -117,6 +119,21 @@ class PoseOptFrame(C.Structure):
 class PoseOptTrace(C.Structure):
     """ft_pose_opt_trace: per round the iterations, the rejected trials and the last currentChi"""
     _fields_ = [("iterations", C.c_int * 4), ("rejected", C.c_int * 4), ("chi2", C.c_double * 4)]
+
+
+class Sim3Problem(C.Structure):
+    """ft_sim3_problem: what the constructor and SetRansacParameters of a Sim3Solver read, and the draws of its iterations"""
+    _fields_ = [("n", C.c_int), ("valid", C.c_void_p), ("world_pos1", C.c_void_p), ("world_pos2", C.c_void_p), ("sigma2_1", C.c_void_p),
+                ("sigma2_2", C.c_void_p), ("Tcw1", SE3), ("Tcw2", SE3), ("cam_model1", C.c_int), ("cam1", C.c_float * 8),
+                ("cam_model2", C.c_int), ("cam2", C.c_float * 8), ("fix_scale", C.c_int), ("probability", C.c_double),
+                ("min_inliers", C.c_int), ("max_iterations", C.c_int), ("rand_draws", C.c_void_p)]
+
+
+class Sim3Result(C.Structure):
+    """ft_sim3_result: the out-parameters of Sim3Solver::iterate and the GetEstimated* getters"""
+    _fields_ = [("converged", C.c_int), ("no_more", C.c_int), ("iterations", C.c_int), ("effective_iterations", C.c_int),
+                ("n_inliers", C.c_int), ("n_best_inliers", C.c_int), ("best_iteration", C.c_int), ("T12", C.c_float * 16),
+                ("R", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float)]
 
 
 class FusePoints(C.Structure):
@@ -310,6 +327,7 @@ def lib() -> C.CDLL:
     L.ft_search_and_triangulate.argtypes = [vp, C.POINTER(TriangKeyFrame), NG, i, C.POINTER(TriangKeyFrame), NG, C.POINTER(TriangPair), i, i, i,
                                             i, i, f, f, vp, vp, vp, vp, vp, vp, vp]
     L.ft_pose_optimization.argtypes = [vp, i, C.POINTER(PoseOptFrame), C.POINTER(SE3), C.POINTER(vp), vp, C.POINTER(PoseOptTrace)]
+    L.ft_sim3_solver.argtypes = [vp, i, C.POINTER(Sim3Problem), C.POINTER(Sim3Result), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.ft_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseTarget), vp, vp, vp, vp]
     L.ft_search_keyframe_sim3.argtypes = [vp, C.POINTER(FrameView), i, C.POINTER(Sim3Job)]
     L.ft_distinctive_descriptors.argtypes = [vp, i, vp, vp, vp, vp, vp]

@@ -590,6 +590,43 @@ struct FtPoseOptCall {
 };
 int ft_launch_pose_opt(hipStream_t st, const FtPoseOptCall &T);
 
+// Sim3Solver (src/Sim3Solver.cc; kernels_sim3_solver.hip) for every problem of a call: three launches whatever the problems hold - a
+// lane per (job, iteration) computes the hypothesis, a wave per (job, iteration) counts its inliers, a workgroup per job selects.
+// One arena as above.  The host gathers the valid pairs of a problem in index order into records (sim3_solver.cpp); a problem with
+// fewer pairs than min_inliers is answered by the host and has no job.
+struct FtSim3Pair {
+    float X1[3], max1;  // mvX3Dc1, mvnMaxError1
+    float X2[3], max2;  // mvX3Dc2, mvnMaxError2
+    float P1[2], P2[2];  // mvP1im1, mvP2im2
+};
+struct FtSim3Hyp {
+    float T12[12], T21[12];  // mT12i, mT21i: the rows [sR | t] of the upper 3 x 4
+    float R[9], s;           // mR12i, ms12i
+    float pad[2];
+};
+struct FtSim3SolverJob {
+    unsigned pairs;   // FtSim3Pair[N]
+    unsigned draws;   // int[3 * eff]: rand() of the iterations
+    unsigned hyps;    // device only: FtSim3Hyp[eff]
+    unsigned counts;  // int[eff]: mnInliersi
+    unsigned out;     // FtSim3SolverOut
+    unsigned flags;   // uint8[N]: mvbBestInliers
+    int N, eff, minInliers, fixScale, model1, model2;  // eff: mRansacMaxIts as SetRansacParameters leaves it
+    float cam1[8], cam2[8];
+};
+struct FtSim3SolverOut {
+    int converged, iterations, nBest, best;  // best: the iteration (from 0) whose hypothesis is mBest*
+    FtSim3Hyp hyp;
+};
+struct FtSim3SolverCall {
+    uint8_t *arena;
+    unsigned jobs;  // FtSim3SolverJob[nJobs]
+    int nJobs, maxEff;
+};
+int ft_launch_sim3_hypotheses(hipStream_t st, const FtSim3SolverCall &T);
+int ft_launch_sim3_count(hipStream_t st, const FtSim3SolverCall &T);
+int ft_launch_sim3_select(hipStream_t st, const FtSim3SolverCall &T);
+
 #ifdef __HIPCC__
 // rotation bin of a match (src/ORBmatcher.cc:817-823, 2171-2176): float arithmetic, round() half away from zero; host twin of the pair: rot_hist.h,
 // the filter of a workgroup over them: rot_filter_dev.h

@@ -1442,6 +1442,62 @@ def pose_optimization(ctx: Context, frames, trace=True):
                  trace=[(tr[f].iterations[r], tr[f].rejected[r], tr[f].chi2[r]) for r in range(4)] if trace else None) for f in range(n)]
 
 
+class Sim3Problem:
+    """One Sim3Solver (ft_sim3_problem): valid [n] (the pair survived the constructor's map tests), world_pos1 / world_pos2 [n, 3],
+    sigma2_1 / sigma2_2 [n] (mvLevelSigma2 of each side's keypoint), Tcw1 / Tcw2 as (q, t) or SE3, the two camera models with
+    their parameters, fix_scale, SetRansacParameters' probability / min_inliers / max_iterations, rand_draws [3 * max_iterations]
+    raw rand() values.  pinned: a Context - the arrays are copied into pinned host memory of it.  Owns the arrays."""
+
+    def __init__(self, valid, world_pos1, world_pos2, sigma2_1, sigma2_2, Tcw1, Tcw2, cam_model1, cam1, cam_model2, cam2, fix_scale,
+                 probability, min_inliers, max_iterations, rand_draws, pinned=None):
+        f32 = np.float32
+        self.valid = _pinned_copy(pinned, np.asarray(valid, np.uint8).reshape(-1), np.uint8)
+        n = len(self.valid)
+        self.world_pos1 = _pinned_copy(pinned, np.asarray(world_pos1, f32).reshape(-1, 3), f32)
+        self.world_pos2 = _pinned_copy(pinned, np.asarray(world_pos2, f32).reshape(-1, 3), f32)
+        self.sigma2_1 = _pinned_copy(pinned, np.asarray(sigma2_1, f32).reshape(-1), f32)
+        self.sigma2_2 = _pinned_copy(pinned, np.asarray(sigma2_2, f32).reshape(-1), f32)
+        assert len(self.world_pos1) == len(self.world_pos2) == len(self.sigma2_1) == len(self.sigma2_2) == n
+        self.rand_draws = np.ascontiguousarray(rand_draws, np.int32).reshape(-1)
+        assert len(self.rand_draws) >= 3 * int(max_iterations)
+        as_se3 = lambda T: T if isinstance(T, SE3) else SE3(T[0], T[1])
+        self.Tcw1, self.Tcw2 = as_se3(Tcw1), as_se3(Tcw2)
+        c = _capi.Sim3Problem()
+        c.n, c.cam_model1, c.cam_model2, c.fix_scale = n, int(cam_model1), int(cam_model2), int(bool(fix_scale))
+        c.valid, c.world_pos1, c.world_pos2 = ptr(self.valid), ptr(self.world_pos1), ptr(self.world_pos2)
+        c.sigma2_1, c.sigma2_2, c.rand_draws = ptr(self.sigma2_1), ptr(self.sigma2_2), ptr(self.rand_draws)
+        c.cam1[:] = [float(v) for v in np.asarray(cam1, f32)]
+        c.cam2[:] = [float(v) for v in np.asarray(cam2, f32)]
+        c.Tcw1, c.Tcw2 = self.Tcw1.c, self.Tcw2.c
+        c.probability, c.min_inliers, c.max_iterations = float(probability), int(min_inliers), int(max_iterations)
+        self.c = c
+
+
+def sim3_solver(ctx: Context, problems, best_inliers=True, hypothesis_inliers=True):
+    """Sim3Solver (src/Sim3Solver.cc) run to bConverge || bNoMore for every Sim3Problem of `problems` in one call (ft_sim3_solver)
+    -> per problem dict(converged, no_more, iterations, effective_iterations, n_inliers, n_best_inliers, best_iteration, T12 [4, 4],
+    R [3, 3], t [3], s float32, inliers [n] uint8 = vbInliers, best_inliers [n] = mvbBestInliers or None, hypothesis_inliers
+    [effective_iterations] int32 = mnInliersi of every iteration or None)"""
+    n = len(problems)
+    P = (_capi.Sim3Problem * max(n, 1))(*[p.c for p in problems])
+    R = (_capi.Sim3Result * max(n, 1))()
+    inl = [np.zeros(max(p.c.n, 1), np.uint8) for p in problems]
+    best = [np.zeros(max(p.c.n, 1), np.uint8) for p in problems] if best_inliers else None
+    hyp = [np.full(p.c.max_iterations, -1, np.int32) for p in problems] if hypothesis_inliers else None
+    arr = lambda v: None if v is None else (C.c_void_p * max(n, 1))(*[ptr(a) for a in v])
+    check(lib().ft_sim3_solver(ctx._h, n, P, R, arr(inl), arr(best), arr(hyp)))
+    out = []
+    for k, p in enumerate(problems):
+        r = R[k]
+        out.append(dict(converged=bool(r.converged), no_more=bool(r.no_more), iterations=r.iterations,
+                        effective_iterations=r.effective_iterations, n_inliers=r.n_inliers, n_best_inliers=r.n_best_inliers,
+                        best_iteration=r.best_iteration, T12=np.array(r.T12[:], np.float32).reshape(4, 4),
+                        R=np.array(r.R[:], np.float32).reshape(3, 3), t=np.array(r.t[:], np.float32), s=np.float32(r.s),
+                        inliers=inl[k][:p.c.n], best_inliers=None if best is None else best[k][:p.c.n],
+                        hypothesis_inliers=None if hyp is None else hyp[k][:r.effective_iterations]))
+    return out
+
+
 def inv_level_sigma2(scale_factors):
     """mvInvLevelSigma2 as ORBextractor builds it: 1.0f / (mvScaleFactor[i] * mvScaleFactor[i])"""
     sf = np.asarray(scale_factors, np.float32)

@@ -966,6 +966,98 @@ FT_API int ft_pose_optimization(ft_context *ctx, int n_frames, const ft_pose_opt
                                 int *n_inliers /* [n_frames] */, ft_pose_opt_trace *trace /* [n_frames] or NULL */);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sim3Solver (src/Sim3Solver.cc): the RANSAC over Horn's closed-form Sim3 that LoopClosing::DetectCommonRegionsFromBoW runs per
+ * candidate between SearchByBoW (ft_search_by_bow_keyframes) and SearchByProjection(KeyFrame, Sim3) (ft_search_keyframe_sim3)
+ * (src/LoopClosing.cc:698-710).  n_problems INDEPENDENT solvers per call - the loop and merge candidates of a keyframe - and all
+ * hypotheses of all of them in THREE launches whatever n_problems is (kernel.sim3_hypotheses: a lane per (problem, iteration);
+ * kernel.sim3_count: a wave per (problem, iteration); kernel.sim3_select: a workgroup per problem), one copy up, one copy down,
+ * one wait; statistics sim3_solver.total, sim3_solver.launches.  No CPU path.
+ *
+ * One problem is one Sim3Solver object driven as its only call site drives it: SetRansacParameters(probability, min_inliers,
+ * max_iterations) (:123-147), then iterate(20, ...) (:218-294) until bConverge || bNoMore - the solver's state persists between
+ * the chunks of 20, so the chunking has no effect; find() (:296-300) is the same loop.
+ * The constructor (:35-121): of the n = mN1 entries of vpMatched12 those with valid[i] != 0 survived the pointer, isBad() and
+ * index tests of :73-91 (the caller's, on its map) and form the N pairs, in index order: mvX3Dc1 / mvX3Dc2 = Rcw * X + tcw of
+ * world_pos1 / world_pos2 (float; Rcw the rotation matrix of Tcw.q; a three-term sum is e0 + (e1 + e2)), mvnMaxError1 / 2 =
+ * 9.210 * sigma2 (a double product rounded to float), mvP1im1 / mvP2im2 = pCamera->project of the camera-frame points (made on the
+ * host with the device's text), mvnIndices1.  sigma2_1 / sigma2_2 are mvLevelSigma2[kp.octave] of each side PER PAIR: the constructor
+ * reads the second through pKFm (as written, :40-45 and :84-85, pKFm is pKF2 for every pair - bDifferentKFs is set only when the
+ * vector was empty; the interface does not depend on that).  The two cameras may be of different models.
+ * SetRansacParameters: epsilon = (float)min_inliers / N; nIterations = ceil(log(1 - probability) / log(1 - pow(epsilon, 3))) in
+ * double, 1 when min_inliers == N; mRansacMaxIts = max(1, min(nIterations, max_iterations)) - result.effective_iterations.
+ * NOT the reference's: the min is taken in DOUBLE, an infinite or NaN quotient counting as more than max_iterations (the
+ * reference converts the double to int first, which is undefined for a small epsilon).
+ * An iteration (:245-263): three draws pick three distinct pairs - rand_draws holds raw rand() values, three per iteration in the
+ * reference's order; each is reduced as DUtils::Random::RandomInt does, int((double)r / (RAND_MAX + 1.0) * d), d = N, N - 1, N - 2,
+ * against a fresh copy of mvAllIndices with the swap-with-back removal of :177-185.  NOT the reference's: every one of the
+ * effective iterations is evaluated and consumes its three draws (the first 3 * effective_iterations entries are read, all
+ * 3 * max_iterations are checked), where the reference stops drawing when it converges.
+ * ComputeSim3 (:311-414): every float step in the reference's order without contraction - centroids (rowwise().sum() / 3), M =
+ * Pr2 * Pr1^T, the ten N entries as float sums, ang = atan2f(|vec|, q0), vec = 2 ang vec / |vec| unless |vec| == 0,
+ * Sophus::SO3f::exp with its small-angle branch (theta^2 < 1e-5f * 1e-5f), sinf / cosf / atan2f as glibc evaluates them, the
+ * quaternion's matrix, P3 = R * Pr2, ms12i = (float)((double)nom / (double)den) or 1.0f with fix_scale, mt12i = O1 - (s R) O2,
+ * mT12i, mT21i with sRinv = (float)(1.0 / s) * R^T and tinv = (-sRinv) * t.  NOT the reference's, each to its rounding error:
+ *   the eigenvector of N's largest eigenvalue is Eigen::EigenSolver<Matrix4f>'s in the reference (a real-Schur solver run on a
+ *   symmetric matrix); here a cyclic two-sided Jacobi in DOUBLE on the float N: pivots (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) per
+ *   sweep, a pivot rotated away unless it is 0 or at most 1e-18 (|app| + |aqq|), until a sweep rotates nothing or 30 sweeps; the
+ *   largest diagonal entry, the first on a tie; the sign normalised to q0 >= 0 (the rotation does not depend on it; ang and the
+ *   bits do); narrowed to float.  For a degenerate sample (a repeated largest eigenvalue: collinear or coincident points)
+ *   agreement with Eigen is not defined;
+ *   nom and den, sums of nine float products, are added one after the other in column-major order (Eigen's reduction order of a
+ *   3 x 3 array is not pinned).
+ * A NaN or infinite scale (den == 0: three coincident points) makes every error NaN, err < max false and the count 0.
+ * CheckInliers (:417-441): per pair P3Dc = R X + t of mT12i on mvX3Dc2 through camera 1 and of mT21i on mvX3Dc1 through camera
+ * 2 (neither projection tests the depth), the squared distances to mvP1im1 / mvP2im2, inlier when err1 < max1 && err2 < max2.
+ * The selection of iterate, evaluated on the counts: the run stops at the first iteration whose count is > min_inliers (an
+ * earlier, larger count would have stopped it), else after effective_iterations; mBest* is the LAST iteration up to the stop
+ * whose count equals the largest of that prefix (the test at :265 is >=).
+ *
+ * result[p]: converged = bConverge, no_more = bNoMore, iterations = mnIterations at exit, n_inliers = nInliers (the count when
+ * converged, else 0), T12 = mBestT12 row-major (what iterate returns when it converged, and the best so far when it did not),
+ * R / t / s / n_best_inliers = GetEstimatedRotation / Translation / Scale and mnBestInliers, best_iteration = the iteration (from
+ * 1) that set them.  inliers[p][n] = vbInliers: all 0 unless converged, then mvbInliersi scattered through mvnIndices1;
+ * best_inliers[p][n] (best_inliers may be NULL) = mvbBestInliers scattered the same way; entries with valid == 0 are written 0.
+ * hypothesis_inliers[p][max_iterations] (may be NULL): mnInliersi of every evaluated iteration, effective_iterations entries -
+ * those behind the stop included; the rest is untouched.
+ * A problem with N < min_inliers has no job (:225-229): no_more = 1, identity, s = 1, no inliers, 0 iterations,
+ * effective_iterations = 0; a call without a job makes no launch.
+ * FT_ERR_INVALID: null arrays, n outside [0, 2^16), an unknown camera model, Tcw1.q / Tcw2.q not a unit quaternion, probability
+ * outside (0, 1), min_inliers < 0, max_iterations < 1, a draw outside [0, FT_SIM3_RAND_MAX], n_problems outside [0, 2^16), and
+ * min_inliers <= N < 3 (the reference draws from an empty list).  FT_ERR_CAPACITY: max_iterations > FT_SIM3_MAX_ITERATIONS (the
+ * reference's call site asks for 300).  Nothing is written on an error.
+ * ---------------------------------------------------------------------------------------------- */
+#define FT_SIM3_MAX_ITERATIONS 1024
+#define FT_SIM3_RAND_MAX 2147483647 /* RAND_MAX of the reference's platform (glibc) */
+typedef struct ft_sim3_problem {
+    int n;                    /* mN1 = vpMatched12.size() */
+    const uint8_t *valid;     /* [n] the pair survived :73-91 */
+    const float *world_pos1;  /* n x 3 pMP1->GetWorldPos(); read where valid */
+    const float *world_pos2;  /* n x 3 pMP2->GetWorldPos() */
+    const float *sigma2_1;    /* [n] pKF1->mvLevelSigma2[kp1.octave] */
+    const float *sigma2_2;    /* [n] pKFm->mvLevelSigma2[kp2.octave] */
+    ft_se3 Tcw1, Tcw2;        /* pKF1->GetPose(), pKF2->GetPose() */
+    int cam_model1;           /* 0 Pinhole, 1 KannalaBrandt8: pKF1->mpCamera */
+    float cam1[8];
+    int cam_model2;           /* pKF2->mpCamera */
+    float cam2[8];
+    int fix_scale;            /* bFixScale */
+    double probability;       /* SetRansacParameters: 0.99 */
+    int min_inliers;          /* nBoWInliers */
+    int max_iterations;       /* 300 */
+    const int *rand_draws;    /* [3 * max_iterations] rand() */
+} ft_sim3_problem;
+typedef struct ft_sim3_result {
+    int converged, no_more, iterations, effective_iterations;
+    int n_inliers, n_best_inliers, best_iteration;
+    float T12[16];
+    float R[9], t[3], s;
+} ft_sim3_result;
+FT_API int ft_sim3_solver(ft_context *ctx, int n_problems, const ft_sim3_problem *problems /* [n_problems] */,
+                          ft_sim3_result *results /* [n_problems] */, uint8_t *const *inliers /* [n_problems] of [n] */,
+                          uint8_t *const *best_inliers /* [n_problems] of [n], or NULL */,
+                          int *const *hypothesis_inliers /* [n_problems] of [max_iterations], or NULL */);
+
+/* ------------------------------------------------------------------------------------------------
  * ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, th, bRight) (src/ORBmatcher.cc:1247-1437) and
  * ORBmatcher::Fuse(KeyFrame *pKF, Sophus::Sim3f &Scw, vpPoints, th, vpReplacePoint) (:1439-1554): the searches
  * LocalMapping::SearchInNeighbors runs for each of its 20 - 40 target keyframes and both cameras, then for the current keyframe

@@ -765,6 +765,42 @@ inline std::vector<int> PoseOptimization(Context &ctx, const std::vector<ft_pose
     return inliers;
 }
 
+// Sim3Solver (src/Sim3Solver.cc) for the candidates of a keyframe in one call (ft_sim3_solver): per problem what
+//   Sim3Solver solver(pKF1, pKF2, vpMatched12, bFixScale, vpKeyFrameMatchedMP); solver.SetRansacParameters(p, minInliers, maxIts);
+//   while (!bConverge && !bNoMore) mTcm = solver.iterate(20, bNoMore, vbInliers, nInliers, bConverge);
+// (src/LoopClosing.cc:698-710) leaves behind.  results[p] onto the out-parameters: bNoMore = no_more, bConverge = converged,
+// nInliers = n_inliers, mTcm = T12 (row-major Matrix4f); onto the getters: GetEstimatedRotation() = R (row-major),
+// GetEstimatedTranslation() = t, GetEstimatedScale() = s, so that gScm = g2o::Sim3(R, t, s) as at :746; mnBestInliers =
+// n_best_inliers.  vbInliers[p] is resized to the problem's n and holds iterate's vbInliers; bestInliers (may be null) receives
+// mvbBestInliers, hypothesisInliers (may be null) mnInliersi of every evaluated iteration (effective_iterations entries).
+inline void Sim3SolverBatch(Context &ctx, const std::vector<ft_sim3_problem> &vProblems, std::vector<ft_sim3_result> &results,
+                            std::vector<std::vector<uint8_t>> &vbInliers, std::vector<std::vector<uint8_t>> *bestInliers = nullptr,
+                            std::vector<std::vector<int>> *hypothesisInliers = nullptr) {
+    const size_t n = vProblems.size();
+    results.assign(n + 1, ft_sim3_result{});
+    vbInliers.resize(n);
+    if (bestInliers) bestInliers->resize(n);
+    if (hypothesisInliers) hypothesisInliers->resize(n);
+    std::vector<uint8_t *> in(n + 1, nullptr), best(n + 1, nullptr);
+    std::vector<int *> hyp(n + 1, nullptr);
+    for (size_t p = 0; p < n; p++) {
+        const size_t np = vProblems[p].n > 0 ? (size_t)vProblems[p].n : 0;
+        vbInliers[p].assign(np + 1, 0);
+        in[p] = vbInliers[p].data();
+        if (bestInliers) (*bestInliers)[p].assign(np + 1, 0), best[p] = (*bestInliers)[p].data();
+        if (hypothesisInliers)
+            (*hypothesisInliers)[p].assign(vProblems[p].max_iterations > 0 ? (size_t)vProblems[p].max_iterations : 1, 0), hyp[p] = (*hypothesisInliers)[p].data();
+    }
+    check(ft_sim3_solver(ctx.handle(), (int)n, vProblems.data(), results.data(), in.data(), bestInliers ? best.data() : nullptr,
+                         hypothesisInliers ? hyp.data() : nullptr));
+    results.resize(n);
+    for (size_t p = 0; p < n; p++) {
+        vbInliers[p].pop_back();
+        if (bestInliers) (*bestInliers)[p].pop_back();
+        if (hypothesisInliers) (*hypothesisInliers)[p].resize((size_t)results[p].effective_iterations);
+    }
+}
+
 // ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) (src/ORBmatcher.cc:1247-1437) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)
 // (:1439-1554) for one list of map points against every target (keyframe, camera) of LocalMapping::SearchInNeighbors or
 // LoopClosing::SearchAndFuse in one call (ft_fuse_search).  vpMapPoints are the arrays of the points, vTargets one record per
