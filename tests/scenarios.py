@@ -34,6 +34,36 @@ def fisheye_frame_scenario(width, height, nfeatures, seed):
     return fr
 
 
+def padded_in_front(fr, n_total, seed, width, height):
+    """A two-camera frame of exactly n_total keypoints without an extraction that large: the keypoints of `fr`
+    (fisheye_frame_scenario's) with padding keypoints IN FRONT of them in each camera's arrays, half of the padding per camera (the
+    odd one goes to the right camera).  A padding keypoint lies uniformly inside the 20 px border, at octave 0 .. 7, with a random
+    angle, size 31 and a random descriptor; it has no left <-> right match.  The real keypoints keep their order, their match
+    tables are shifted by the other camera's padding - so the real right-camera keypoints hold the highest indices of the frame.
+    One seeded generator, host arrays only.  -> dict(kL, kR, dL, dR, l2r, r2l, padL, padR)"""
+    rng = np.random.default_rng(seed)
+    nl, nr = len(fr["kL"]), len(fr["kR"])
+    pad = n_total - nl - nr
+    assert pad >= 0, "the base frame has more keypoints than n_total"
+    padL = pad // 2
+    padR = pad - padL
+
+    def camera(keys, desc, n):
+        k = np.zeros(n, KP)
+        k["x"] = rng.uniform(20.0, width - 20.0, n)
+        k["y"] = rng.uniform(20.0, height - 20.0, n)
+        k["size"] = 31.0
+        k["angle"] = rng.uniform(0.0, 360.0, n)
+        k["octave"] = rng.integers(0, 8, n)
+        k["class_id"] = -1
+        d = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        return np.concatenate([k, keys]), np.concatenate([d, desc])
+    kL, dL = camera(fr["kL"], fr["dL"], padL)
+    kR, dR = camera(fr["kR"], fr["dR"], padR)
+    l2r = np.concatenate([np.full(padL, -1, np.int32), np.where(fr["l2r"] >= 0, fr["l2r"] + padR, -1).astype(np.int32)])
+    r2l = np.concatenate([np.full(padR, -1, np.int32), np.where(fr["r2l"] >= 0, fr["r2l"] + padL, -1).astype(np.int32)])
+    return dict(kL=kL, kR=kR, dL=dL, dR=dR, l2r=l2r, r2l=r2l, padL=padL, padR=padR)
+
 
 def two_camera_points(fr, sf, seed, M=1200, zero_obs_frac=0.2):
     rng = np.random.default_rng(seed)

@@ -10,7 +10,11 @@ trials use windows so wide that candidate lists outgrow the cache (resolution fa
 --geometry draws image bounds (every side of the image rectangle moved by up to 45 px, fractional) and a number of pyramid levels
 (1 - 12) per frame and a pyramid factor (1.1 / 1.2 / 1.5 / 2.0: one log scale factor serves a track_local_map call) per trial, from a
 generator of its own: without the flag the trial stream is what it always was.
-usage: tests/tools/soak_batch.py [--trials N] [--seed S] [--frames B] [--geometry]      exit code 1 on any mismatch"""
+--large pads, in a quarter of the trials, one two-camera frame of the batch to 12 288 .. 17 000 keypoints (scenarios.padded_in_front:
+padding in front of the real keypoints of each camera) - the sizes around which k_resolve_batch (12 288) and k_replay_batch (15 360)
+move their last-writer tables from LDS to HBM, for every frame of the batch - drawn from a generator of its own as well; the report
+counts the trials per table regime.
+usage: tests/tools/soak_batch.py [--trials N] [--seed S] [--frames B] [--geometry] [--large]      exit code 1 on any mismatch"""
 import argparse
 import os
 import sys
@@ -27,6 +31,8 @@ import scenarios as sc  # noqa: E402
 
 TRL = np.concatenate([np.eye(3), [[-0.101], [0.0], [0.0]]], 1).astype(np.float32)
 TLR = (0.101, 0.0, 0.0)
+LARGE_SIZES = (12288, 12289, 14000, 15360, 15361, 17000)   # --large: on and around the thresholds of tracked_batch.cpp
+RESOLVE_LDS_MAX, REPLAY_LDS_MAX = 12288, 15360
 
 
 def main(argv=None):
@@ -35,15 +41,18 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--geometry", action="store_true", help="random image bounds and pyramid depth per frame, pyramid factor per trial")
+    ap.add_argument("--large", action="store_true", help="a quarter of the trials: one two-camera frame padded to 12 288 .. 17 000 keypoints")
     args = ap.parse_args(argv)
     rng = np.random.default_rng(args.seed)
     grng = np.random.default_rng([args.seed, 0x6e0])   # the geometry's own stream: the trials themselves stay what they were
+    lrng = np.random.default_rng([args.seed, 0x1a46e])   # --large's own stream, for the same reason
     ctx = orb.Context(0)
     sf, _ = ob.scale_factors(1.2, 8)
     B = args.frames
-    tb = orb.TrackedBatch(ctx, max_frames=B, max_keypoints=4400, max_points=2304)
+    tb = orb.TrackedBatch(ctx, max_frames=B, max_keypoints=max(LARGE_SIZES) + 8 if args.large else 4400, max_points=2304)
     fails = frames_n = matches = pinned_trials = 0
     modes = {1: 0, 2: 0, 3: 0}
+    regimes = {"lds": 0, "resolve_hbm": 0, "both_hbm": 0}   # where the largest frame of a trial's batch puts the last-writer tables
     t0 = time.time()
     bases = {}
 
@@ -68,6 +77,8 @@ def main(argv=None):
         nn = float(rng.choice([0.8, 0.6, 0.9]))
         views, lasts, Tcws, ptss, poses, orc = [], [], [], [], [], []
         factor = float(grng.choice([1.1, 1.2, 1.5, 2.0])) if args.geometry else 1.2
+        large_n = int(lrng.choice(LARGE_SIZES)) if args.large and lrng.random() < 0.25 else 0   # (the trial's first two-camera frame)
+        max_n = 0
         log_sf = float(np.float32(np.log(np.float32(factor))))
         for f in range(B):
             kind = int(rng.random() < 0.6)
@@ -87,9 +98,15 @@ def main(argv=None):
                 nr = len(fr["kR"])
                 l2r = np.where(fr["l2r"][:nl] < nr, fr["l2r"][:nl], -1).astype(np.int32)
                 r2l = np.where(fr["r2l"] < nl, fr["r2l"], -1).astype(np.int32)
-                hold = np.concatenate([holder, np.full(nr, -1, np.int32)])
-                kw = dict(keys=kL, keys_right=fr["kR"], descriptors=np.concatenate([dL, fr["dR"]]), bounds=bounds,
-                          left_to_right=l2r, right_to_left=r2l, cam_model=1, cam=list(sc.KB8_CAM), Trl=TRL, holder_obs=hold)
+                pad = dict(kL=kL, kR=fr["kR"], dL=dL, dR=fr["dR"], l2r=l2r, r2l=r2l, padL=0, padR=0)
+                if large_n > nl + nr:   # the points below are built on the real keypoints (kL, dL), whatever stands in front of them
+                    pad = sc.padded_in_front(pad, large_n, int(lrng.integers(0, 1 << 30)), w, h)
+                    large_n = 0
+                    for keys, n_pad in ((pad["kL"], pad["padL"]), (pad["kR"], pad["padR"])):
+                        keys["octave"][:n_pad] %= nlev   # (--geometry: the frame may have fewer than eight levels)
+                hold = np.concatenate([np.full(pad["padL"], -1, np.int32), holder, np.full(pad["padR"] + nr, -1, np.int32)])
+                kw = dict(keys=pad["kL"], keys_right=pad["kR"], descriptors=np.concatenate([pad["dL"], pad["dR"]]), bounds=bounds,
+                          left_to_right=pad["l2r"], right_to_left=pad["r2l"], cam_model=1, cam=list(sc.KB8_CAM), Trl=TRL, holder_obs=hold)
                 intr = dict(fx=sc.KB8_CAM[0], fy=sc.KB8_CAM[1], cx=sc.KB8_CAM[2], cy=sc.KB8_CAM[3])
                 depth, uright, tlr = np.zeros(nl, np.float32), None, TLR
             else:
@@ -97,6 +114,7 @@ def main(argv=None):
                 kw = dict(keys=kL, descriptors=dL, bounds=bounds, mbf=intr["mbf"], mb=intr["mb"], uright=uright,
                           holder_obs=holder, cam=[intr[k] for k in ("fx", "fy", "cx", "cy")])
             oF, gF = ob.FrameView(scale_factors_=sf, **kw), orb.FrameView(scale_factors=sf, **kw)
+            max_n = max(max_n, oF.N)
             seed = int(rng.integers(0, 1 << 30))
             last, Tcw = sc.last_frame_scenario(kL, dL, uright, depth, intr, w, h, seed=seed)
             M = int(rng.integers(0, 2001))
@@ -128,6 +146,7 @@ def main(argv=None):
                 g1 = tb.search_last_frame(pl1, th=th)
                 g2 = tb.track_local_map(pl2, viewing_cos_limit=0.5, log_scale_factor=log_sf, th=th, nn_ratio=nn, far_points=far, th_far_points=th_far)
         modes[opts["search_cache"]] += 1
+        regimes["lds" if max_n <= RESOLVE_LDS_MAX else "resolve_hbm" if max_n <= REPLAY_LDS_MAX else "both_hbm"] += 1
         for f in range(B):
             o1, ofr, o2, oF = orc[f]
             what = None
@@ -154,7 +173,8 @@ def main(argv=None):
         fallbacks = 0
     one = modes[3] + (modes[2] if B >= 24 else 0)
     print(f"{args.trials} batches of {B} frames ({one} resolved in one launch, {fallbacks} searches of those fell back to the passes; "
-          f"{args.trials - one} by the passes; {pinned_trials} with the point arrays read in place from pinned memory): {frames_n} frames, {2 * frames_n} searches, {matches} matches, {fails} mismatches, {time.time() - t0:.0f} s")
+          f"{args.trials - one} by the passes; {pinned_trials} with the point arrays read in place from pinned memory; last-writer tables of k_resolve_batch / k_replay_batch: "
+          f"{regimes['lds']} trials LDS / LDS, {regimes['resolve_hbm']} HBM / LDS, {regimes['both_hbm']} HBM / HBM): {frames_n} frames, {2 * frames_n} searches, {matches} matches, {fails} mismatches, {time.time() - t0:.0f} s")
     return 1 if fails else 0
 
 
